@@ -1,9 +1,18 @@
 #!/usr/bin/env python3
 """Baum-Welch throughput benchmark (BASELINE.json metric) on MI355X.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
         --master-port P bench.py --gpus N --steps K --warmup W
+
+A plain run does only what the headline needs: set-up, pre-warm, W warm-up and K timed steps, the JSON line
+(roofline, cpu_baseline and synced are null, no per-launch event batch).  --full adds everything below
+that takes work of its own: the per-launch HIP-event batch and the roofline priced on it, the synced
+protocol and the CPU baseline.  Every timed leg starts from the seeded initial parameters (the reset sits
+before the warm-up), so the K timed steps are EM iterations W+1 .. W+K of the same run every time and
+--dump-outputs DIR can write what the last of them left: pi, A, B (the returned, normalised parameters),
+loglik (log P(O_r) of every sequence of rank 0 at the last E-step) and L_trace (the (L, diff) records of
+the timed steps), one float64 DIR/<name>.npy each.
 
 One step = one full EM iteration (E-step kernel over every sequence of the rank, the RCCL all-reduce
 of the packed statistics when N > 1, the M-step/convergence kernel) on synthetic sequences already
@@ -21,7 +30,7 @@ Dirichlet(0.3) emission rows (skewed symbol counts).
 launcher, --gpus must equal WORLD_SIZE.  --dry-run runs the launcher/rendezvous/timing skeleton
 with no GPU work (CPU tests).
 
-Prints ONE JSON line (rank 0) with the driver's fields plus:
+Prints ONE JSON line (rank 0) with the headline fields (metric, value, unit, ms_per_step, ...) plus, with --full:
   roofline     — SURVEY §8(d) for the dominant launch: algorithmic work over the kernel's launch duration
                  (HIP events on the engine stream) against the bounding resource's peak: bound "hbm",
                  B_u = 24T + 16NT + 8 bytes per sequence vs 8 TB/s on the small kernels (a fixed conversion
@@ -76,6 +85,12 @@ def parse(argv=None):
     p.add_argument("--gpus", type=int, default=1)
     p.add_argument("--steps", type=int, default=200)
     p.add_argument("--warmup", type=int, default=10)
+    p.add_argument("--full", action="store_true",
+                   help="also the per-launch HIP-event batch and the roofline, the synced protocol and the CPU "
+                        "baseline (each still has its own --no-... switch); off: only the headline")
+    p.add_argument("--dump-outputs", default=None, metavar="DIR",
+                   help="after the timed steps write what the last of them computed (pi, A, B, loglik, L_trace) "
+                        "as float64 DIR/<name>.npy (rank 0)")
     p.add_argument("--prewarm-ms", type=float, default=200.0,
                    help="untimed EM iterations for at least this long before the warm-up steps: the GPU clocks "
                         "ramp up over ~35 ms of load after the set-up (profiles/r5/warmup_ramp.txt)")
@@ -572,6 +587,36 @@ def find_same_host():
     return d
 
 
+DUMP_MAX_BYTES = 64 << 20  # --dump-outputs writes at most this much in all
+DUMP_LOGLIK_ROWS = 4_000_000  # loglik rows kept (32 MB): a larger shard is sampled (fixed seed, sorted indices)
+RECORD_RING = 4096  # iteration records the engine keeps (include/hmmbw.h, hmmbw_get_status)
+
+
+def capture_outputs(eng, iterations, steps):
+    """What a caller of the timed path holds after its last step, as float64 host arrays: the returned
+    (normalised) pi, A, B, log P(O_r | lambda) of every local sequence at the last E-step, and the
+    (L, diff) records of the timed steps (the last 4,096 of them at most).  Call after hmmbw_get_status
+    has completed the last step's deferred M-step."""
+    pi, A, B = eng.params(normalise=True)
+    ll = eng.loglik()
+    if ll.size > DUMP_LOGLIK_ROWS:
+        ll = ll[np.sort(np.random.default_rng(0).choice(ll.size, DUMP_LOGLIK_ROWS, replace=False))]
+    n = min(steps, RECORD_RING, iterations)
+    recs = eng.status(iterations - n, n)[1] if n else []
+    return {"pi": pi, "A": A, "B": B, "loglik": np.ascontiguousarray(ll),
+            "L_trace": np.array(recs, dtype=np.float64).reshape(n, 2)}
+
+
+def write_outputs(path, arrays):
+    total = sum(a.nbytes for a in arrays.values())
+    if total > DUMP_MAX_BYTES:
+        raise RuntimeError(f"--dump-outputs: {total} bytes of outputs exceed the {DUMP_MAX_BYTES}-byte limit")
+    os.makedirs(path, exist_ok=True)
+    for name, a in arrays.items():
+        assert a.dtype == np.float64, (name, a.dtype)
+        np.save(os.path.join(path, name + ".npy"), a)
+
+
 def free_port():
     with socket.socket() as s:
         s.bind(("127.0.0.1", 0))
@@ -679,7 +724,12 @@ def main(argv=None):
 
     def leg(steps, warmup):
         """Warm-up, then EXACTLY `steps` EM iterations between barrier + synchronize brackets (max over
-        ranks), then the per-launch timing batch (HIP events) outside the timed region."""
+        ranks), then (--full) the per-launch timing batch (HIP events) outside the timed region.  The leg
+        starts from the initial parameters: however many iterations the time-based pre-warm ran, the timed
+        steps are iterations warmup + 1 .. warmup + steps, the same arithmetic in every run."""
+        eng.set_params(pi, A, B)
+        eng.reset(0.0, 1 << 40)
+        n_iter[0] = 0
         enqueue(warmup)
         torch.cuda.synchronize()
         eng.timing(0)
@@ -715,6 +765,8 @@ def main(argv=None):
             st, _ = eng.status()
             r["error"] = None if st.iterations == n_iter[0] else \
                 f"expected {n_iter[0]} iterations, engine ran {st.iterations}"
+            if args.dump_outputs and rank == 0 and not r["error"]:
+                r["outputs"] = capture_outputs(eng, st.iterations, steps)
         except Exception as e:  # noqa: BLE001 - reported in the JSON line, or raised for the first leg
             r["error"] = str(e)
         if world > 1:
@@ -736,7 +788,7 @@ def main(argv=None):
         if r["error"]:
             r["allreduce"] = eng.allreduce
             return r
-        if not args.no_kernel_timing:
+        if args.full and not args.no_kernel_timing:
             eng.timing(1)
             eng.comm_info(reset=True)
             enqueue(args.timing_batch)
@@ -832,66 +884,18 @@ def main(argv=None):
     kern_ms, kern_n, est_ms, est_n = L["kern_ms"], L["kern_n"], L["est_ms"], L["est_n"]
     ar_ms, ar_n, comm_ranks = L["ar_ms"], L["ar_n"], L["comm_ranks"]
     st, _ = eng.status()
+    if args.dump_outputs and rank == 0:
+        write_outputs(args.dump_outputs, L["outputs"])
 
     synced = None
-    if not args.no_synced:
+    if args.full and not args.no_synced:
         synced = synced_protocol(eng, stats, world, dist, R)
 
     ms_step = 1000.0 * elapsed / args.steps
     value = R * world * args.steps / elapsed
-    # the kernel time the roofline uses: single rank on the small kernels, every step is ONE launch
-    # (E-step with the merged M-step), so the GPU time per step over the timed region IS the launch
-    # duration (+ the ~1 us dispatch gap between back-to-back launches: conservative); elsewhere (the
-    # wide path's three launches, the all-reduce of N > 1) the per-launch event batch above
-    single_kernel = world == 1 and N <= 16 and not args.deterministic
-    if single_kernel or kern_n == 0:
-        kern_s, kern_src = gpu_ms_step / 1000.0, "HIP events around the timed region / steps (one launch per step)"
-    else:
-        kern_s, kern_src = kern_ms / kern_n / 1000.0, f"HIP events around each of {kern_n} E-step launches after the timed region"
-    bu = bytes_per_sequence(T, N)
-    wide = N > 16
-    cfg_key = f"R{R}_T{T}_N{N}_K{K}_{topo}" + ("_H" if args.symbols == "H" else "")
-    traffic = find_traffic(cfg_key)
-    issue = find_issue(cfg_key)
-    estep_s = (est_ms / est_n / 1000.0) if est_n else None
-    lmap = eng.launch_map()
-    small_kernel = "k_estep_join" if lmap.get("joined") else "k_estep_small"  # the joined map's 8-wave kernel
-    bounds = roofline_bounds(R, T, N, kern_s, traffic, issue, estep_s, lmap, topo)
-    # The roofline (the task's contract and SURVEY §8(d)): ALGORITHMIC work per launch over the kernel's
-    # average launch duration against the peak of the bounding resource.  Small kernels: HBM, B_u = 24T +
-    # 16NT + 8 bytes per sequence (a fixed conversion: it charges an alpha_hat round trip the
-    # checkpoint-and-recompute kernels never make, so frac can exceed 1).  Wide path: the fp64 matrix
-    # pipe, 8 N^2 T flops per sequence over the E-step kernel.  `binding` is the tightest ceiling the
-    # counters measure (largest achieved / peak among `bounds`, each <= 1 when measurement and model are
-    # right), with the profile it came from and whether that profile was collected on these kernels.
-    b = bounds.get(bounds.get("binding") or "", None)
-    if wide:
-        t_e = estep_s if estep_s else kern_s
-        ach = flops_per_sequence(T, N) * R / t_e / 1e12 if t_e > 0 else float("nan")
-        model = {"bound": "mfma", "achieved": ach, "peak": FP64_MFMA_PEAK_TFS, "unit": "TFLOP/s",
-                 "frac": ach / FP64_MFMA_PEAK_TFS, "units_per_launch": R,
-                 "work_per_unit": f"{flops_per_sequence(T, N)} flops (SURVEY §8(d): 8 N^2 T per sequence)",
-                 "issued_frac_6N2T": mfma_flops_issued(T, N) * R / t_e / 1e12 / FP64_MFMA_PEAK_TFS,
-                 "kernel": "k_estep_mfma", "kernel_ms": 1e3 * t_e}
-    else:
-        ach = bu * R / kern_s / 1e9 if kern_s > 0 else float("nan")
-        model = {"bound": "hbm", "achieved": ach, "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": ach / HBM_PEAK_GBS,
-                 "units_per_launch": R,
-                 "work_per_unit": f"{bu} bytes (SURVEY §8(d): 24 T + 16 N T + 8 per sequence)",
-                 "kernel": small_kernel, "kernel_ms": 1e3 * kern_s}
-    roof = {"bound": model["bound"], "achieved": model["achieved"], "peak": model["peak"], "unit": model["unit"],
-            "frac": model["frac"], "traffic": traffic[0] if traffic else None,
-            "model": model,
-            "kernel": "k_estep_mfma + k_bnum_gather (E-step)" if wide else f"{small_kernel} (E-step)",
-            "kernel_ms": kern_s * 1000.0, "kernel_time_source": kern_src,
-            "binding": ({"resource": bounds["binding"], **{k: b[k] for k in ("achieved", "peak", "unit", "frac")},
-                         "t_bound_us": b.get("t_bound_us"), "provenance": b.get("provenance")} if b else None),
-            "hbm_frac_measured": bounds["hbm"]["frac"] if "hbm" in bounds else None,
-            "traffic_provenance": traffic[2] if traffic else None,
-            "kernel_src_sha16": kernel_source_hash(),
-            "bounds": bounds, "launch_map": lmap,
-            "gpu_ms_per_step": gpu_ms_step,
-            "kernel_ms_per_launch_events": kern_ms / kern_n if kern_n else None}
+    roof = None
+    if args.full:
+        roof = roofline_report(args, eng, world, R, T, N, K, topo, gpu_ms_step, kern_ms, kern_n, est_ms, est_n)
 
     if rank == 0:
         out = {
@@ -937,8 +941,10 @@ def main(argv=None):
             "synced": synced,
             "upload_s": upload_s,
             "loglik_last": st.last_log_likelihood,
+            "outputs": ({"dir": args.dump_outputs, "arrays": {k: list(v.shape) for k, v in L["outputs"].items()}}
+                        if args.dump_outputs else None),
         }
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             out["cpu_baseline"] = cpu_baseline(N, K, T, topo, args.cpu_seconds, seed, args.symbols, args.cpu_threads)
         else:
             out["cpu_baseline"] = None
@@ -947,6 +953,64 @@ def main(argv=None):
     if world > 1:
         dist.destroy_process_group()
     return 0
+
+
+def roofline_report(args, eng, world, R, T, N, K, topo, gpu_ms_step, kern_ms, kern_n, est_ms, est_n):
+    """The JSON line's roofline block (--full): the algorithmic model, every measured bound, the launch map."""
+    # the kernel time the roofline uses: single rank on the small kernels, every step is ONE launch
+    # (E-step with the merged M-step), so the GPU time per step over the timed region IS the launch
+    # duration (+ the ~1 us dispatch gap between back-to-back launches: conservative); elsewhere (the
+    # wide path's three launches, the all-reduce of N > 1) the per-launch event batch of the leg
+    single_kernel = world == 1 and N <= 16 and not args.deterministic
+    if single_kernel or kern_n == 0:
+        kern_s, kern_src = gpu_ms_step / 1000.0, "HIP events around the timed region / steps (one launch per step)"
+    else:
+        kern_s, kern_src = kern_ms / kern_n / 1000.0, f"HIP events around each of {kern_n} E-step launches after the timed region"
+    bu = bytes_per_sequence(T, N)
+    wide = N > 16
+    cfg_key = f"R{R}_T{T}_N{N}_K{K}_{topo}" + ("_H" if args.symbols == "H" else "")
+    traffic = find_traffic(cfg_key)
+    issue = find_issue(cfg_key)
+    estep_s = (est_ms / est_n / 1000.0) if est_n else None
+    lmap = eng.launch_map()
+    small_kernel = "k_estep_join" if lmap.get("joined") else "k_estep_small"  # the joined map's 8-wave kernel
+    bounds = roofline_bounds(R, T, N, kern_s, traffic, issue, estep_s, lmap, topo)
+    # The roofline (SURVEY §8(d)): ALGORITHMIC work per launch over the kernel's
+    # average launch duration against the peak of the bounding resource.  Small kernels: HBM, B_u = 24T +
+    # 16NT + 8 bytes per sequence (a fixed conversion: it charges an alpha_hat round trip the
+    # checkpoint-and-recompute kernels never make, so frac can exceed 1).  Wide path: the fp64 matrix
+    # pipe, 8 N^2 T flops per sequence over the E-step kernel.  `binding` is the tightest ceiling the
+    # counters measure (largest achieved / peak among `bounds`, each <= 1 when measurement and model are
+    # right), with the profile it came from and whether that profile was collected on these kernels.
+    b = bounds.get(bounds.get("binding") or "", None)
+    if wide:
+        t_e = estep_s if estep_s else kern_s
+        ach = flops_per_sequence(T, N) * R / t_e / 1e12 if t_e > 0 else float("nan")
+        model = {"bound": "mfma", "achieved": ach, "peak": FP64_MFMA_PEAK_TFS, "unit": "TFLOP/s",
+                 "frac": ach / FP64_MFMA_PEAK_TFS, "units_per_launch": R,
+                 "work_per_unit": f"{flops_per_sequence(T, N)} flops (SURVEY §8(d): 8 N^2 T per sequence)",
+                 "issued_frac_6N2T": mfma_flops_issued(T, N) * R / t_e / 1e12 / FP64_MFMA_PEAK_TFS,
+                 "kernel": "k_estep_mfma", "kernel_ms": 1e3 * t_e}
+    else:
+        ach = bu * R / kern_s / 1e9 if kern_s > 0 else float("nan")
+        model = {"bound": "hbm", "achieved": ach, "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": ach / HBM_PEAK_GBS,
+                 "units_per_launch": R,
+                 "work_per_unit": f"{bu} bytes (SURVEY §8(d): 24 T + 16 N T + 8 per sequence)",
+                 "kernel": small_kernel, "kernel_ms": 1e3 * kern_s}
+    roof = {"bound": model["bound"], "achieved": model["achieved"], "peak": model["peak"], "unit": model["unit"],
+            "frac": model["frac"], "traffic": traffic[0] if traffic else None,
+            "model": model,
+            "kernel": "k_estep_mfma + k_bnum_gather (E-step)" if wide else f"{small_kernel} (E-step)",
+            "kernel_ms": kern_s * 1000.0, "kernel_time_source": kern_src,
+            "binding": ({"resource": bounds["binding"], **{k: b[k] for k in ("achieved", "peak", "unit", "frac")},
+                         "t_bound_us": b.get("t_bound_us"), "provenance": b.get("provenance")} if b else None),
+            "hbm_frac_measured": bounds["hbm"]["frac"] if "hbm" in bounds else None,
+            "traffic_provenance": traffic[2] if traffic else None,
+            "kernel_src_sha16": kernel_source_hash(),
+            "bounds": bounds, "launch_map": lmap,
+            "gpu_ms_per_step": gpu_ms_step,
+            "kernel_ms_per_launch_events": kern_ms / kern_n if kern_n else None}
+    return roof
 
 
 def synced_protocol(eng, stats, world, dist, R, iters=10, dropin_iters=20):

@@ -60,7 +60,7 @@ def test_skewed_symbols_are_skewed_and_seeded():
 
 @pytest.mark.gpu
 def test_bench_single_gpu_line():
-    r = subprocess.run([sys.executable, "bench.py", "--steps", "10", "--warmup", "2", "--cpu-seconds", "1"],
+    r = subprocess.run([sys.executable, "bench.py", "--full", "--steps", "10", "--warmup", "2", "--cpu-seconds", "1"],
                        cwd=ROOT, capture_output=True, text=True, timeout=600)
     assert r.returncode == 0, r.stderr[-3000:]
     d = _json_line(r.stdout)
@@ -81,6 +81,59 @@ def test_bench_single_gpu_line():
     assert rf["launch_map"]["waves"] == 1250 and rf["launch_map"]["extra_waves"] == 2
     assert bd["waves_on_busiest_simd"] == 2 and bd["waves_on_busiest_cu"] == 6
     assert rf["kernel_src_sha16"] and d["cpu_baseline"]["value"] > 0
+
+
+def test_plain_run_is_the_default():
+    sys.path.insert(0, ROOT)
+    import bench
+    a = bench.parse(["--gpus", "1", "--steps", "7", "--warmup", "3"])
+    assert a.full is False and a.dump_outputs is None and a.steps == 7 and a.warmup == 3
+    a = bench.parse(["--full", "--dump-outputs", "d"])
+    assert a.full is True and a.dump_outputs == "d"
+
+
+@pytest.mark.gpu
+def test_bench_plain_run_dumps_the_last_timed_step(tmp_path):
+    """A plain run (no --full) prints the headline only, and --dump-outputs writes what the timed steps left:
+    however long the time-based pre-warm ran, the timed steps are EM iterations warmup + 1 .. warmup + steps
+    from the seeded initial parameters, so an engine run of the same 5 iterations in this process gives the
+    same arrays (same kernels; fp atomics reorder sums of ~1e5 terms: 1e-9 relative is far above that)."""
+    import numpy as np
+    sys.path.insert(0, ROOT)
+    import bench
+    from hmm_training_amd.engine import BaumWelchEngine
+    R, T, N, K, W, S = 600, 200, 8, 256, 2, 3
+    out = tmp_path / "dump"
+    r = subprocess.run([sys.executable, "bench.py", "--gpus", "1", "--steps", str(S), "--warmup", str(W), "--R", str(R),
+                        "--prewarm-ms", "5", "--dump-outputs", str(out)], cwd=ROOT, capture_output=True, text=True,
+                       timeout=300)
+    assert r.returncode == 0, r.stderr[-3000:]
+    d = _json_line(r.stdout)
+    for k in REQUIRED:
+        assert k in d, k
+    assert d["steps"] == S and d["value"] > 0 and d["ms_per_step"] > 0 and d["dtype"] == "f64"
+    assert d["value"] == pytest.approx(R * 1000.0 / d["ms_per_step"])
+    assert d["roofline"] is None and d["cpu_baseline"] is None and d["synced"] is None
+    got = {n: np.load(out / f"{n}.npy") for n in ("pi", "A", "B", "loglik", "L_trace")}
+    assert sorted(p.name for p in out.iterdir()) == sorted(f"{n}.npy" for n in got)
+    assert all(a.dtype == np.float64 for a in got.values())
+    assert got["loglik"].shape == (R,) and got["L_trace"].shape == (S, 2) and got["B"].shape == (N, K)
+    pi, A, B = bench.init_params(N, K, "left_to_right", np.random.default_rng(3))
+    with BaumWelchEngine(N, K, device=0, topology="left_to_right") as eng:
+        eng.set_observations(offsets=np.arange(R + 1, dtype=np.int64) * T,
+                             symbols=bench.synthetic_symbols(R, T, N, K, "U", 3), n_seq_global=R)
+        eng.set_params(pi, A, B)
+        eng.reset(0.0, 1 << 40)
+        eng.enqueue_iterations(W + S)
+        st, recs = eng.status(W, S)
+        want = dict(zip(("pi", "A", "B"), eng.params(normalise=True)), loglik=eng.loglik(), L_trace=np.array(recs))
+    assert st.iterations == W + S and d["loglik_last"] == pytest.approx(st.last_log_likelihood, rel=1e-9)
+    for n in ("pi", "A", "B", "loglik"):
+        np.testing.assert_allclose(got[n], want[n], rtol=1e-9, atol=1e-15, err_msg=n)
+    # L to 1e-9 relative; diff is a difference of two consecutive L's, so it carries their absolute error
+    np.testing.assert_allclose(got["L_trace"][:, 0], want["L_trace"][:, 0], rtol=1e-9)
+    np.testing.assert_allclose(got["L_trace"][:, 1], want["L_trace"][:, 1], rtol=1e-9,
+                               atol=2e-9 * np.abs(want["L_trace"][:, 0]).max())
 
 
 @pytest.mark.gpu
@@ -105,7 +158,7 @@ def test_bench_self_spawned_two_ranks_one_gpu_gloo():
     """`bench.py --gpus 2` without a launcher on the one-GPU box (both ranks on cuda:0, gloo carrying
     the all-reduce): the real E-step/all-reduce/M-step loop, n_gpus 2 in the line."""
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK")}
-    r = subprocess.run([sys.executable, "bench.py", "--gpus", "2", "--steps", "5", "--warmup", "1", "--R", "2000",
+    r = subprocess.run([sys.executable, "bench.py", "--full", "--gpus", "2", "--steps", "5", "--warmup", "1", "--R", "2000",
                         "--dist-backend", "gloo"], cwd=ROOT, capture_output=True, text=True, timeout=600, env=env)
     assert r.returncode == 0, r.stderr[-3000:]
     d = _json_line(r.stdout)

@@ -36,7 +36,7 @@ def run(spec, case, steps):
         k, _, v = kv.partition("=")
         env[k] = v
     st = steps if case != "cfg5" else max(10, steps // 20)
-    cmd = [sys.executable, "-u", os.path.join(ROOT, "bench.py"), "--no-cpu-baseline", "--no-synced",
+    cmd = [sys.executable, "-u", os.path.join(ROOT, "bench.py"), "--full", "--no-cpu-baseline", "--no-synced",
            "--steps", str(st), "--warmup", "5", *CASES[case]]
     out = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=300)
     if out.returncode != 0:

@@ -6,7 +6,7 @@ TAG=${1:-r3}
 R=${GRAFT_REPO_ROOT:-$(pwd)}
 OUT=$R/gpurun_out/bench_$TAG
 mkdir -p "$OUT"
-run() { local name=$1; shift; timeout -k 10 300 python3 "$R/bench.py" "$@" > "$OUT/$name.log" 2>&1 || exit 1; }
+run() { local name=$1; shift; timeout -k 10 300 python3 "$R/bench.py" --full "$@" > "$OUT/$name.log" 2>&1 || exit 1; }
 run lr_cfg3
 run dense_cfg3 --topology dense --no-cpu-baseline
 run lrH_cfg3 --symbols H --no-cpu-baseline

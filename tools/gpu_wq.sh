@@ -9,7 +9,7 @@ timeout -k 10 900 python -u -m pytest -x -v --timeout 600 --timeout-method threa
 grep -E "passed|failed|PASSED" $OUT/t2.log | tail -12
 for r in 1 2; do
   for w in 1 0; do
-    HMMBW_WIDE_WQ=$w timeout -k 10 200 python -u bench.py --workload cfg5 --steps 10 --warmup 2 --no-cpu-baseline --no-synced > $OUT/cfg5_wq$w.$r.json 2> $OUT/cfg5_wq$w.$r.err || exit 1
+    HMMBW_WIDE_WQ=$w timeout -k 10 200 python -u bench.py --full --workload cfg5 --steps 10 --warmup 2 --no-cpu-baseline --no-synced > $OUT/cfg5_wq$w.$r.json 2> $OUT/cfg5_wq$w.$r.err || exit 1
     python -c "import json; d=json.loads(open('$OUT/cfg5_wq$w.$r.json').read().strip().splitlines()[-1]); print('cfg5 wq=$w', round(d['ms_per_step']*1000,1), 'us/step', d['roofline'].get('kernel_ms'))"
   done
 done

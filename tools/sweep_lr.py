@@ -14,7 +14,7 @@ RUNS = ([(R, 200) for R in (1024, 4096, 8192, 9000, 10000, 11000, 12500, 16384)]
 def main():
     out = open(sys.argv[1], "w") if len(sys.argv) > 1 else None
     for R, T in RUNS:
-        cmd = [sys.executable, "-u", os.path.join(ROOT, "bench.py"), "--R", str(R), "--T", str(T), "--steps", "200",
+        cmd = [sys.executable, "-u", os.path.join(ROOT, "bench.py"), "--full", "--R", str(R), "--T", str(T), "--steps", "200",
                "--no-cpu-baseline", "--no-synced"]
         p = subprocess.run(cmd, capture_output=True, text=True, timeout=240)
         if p.returncode != 0:
