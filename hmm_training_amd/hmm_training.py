@@ -8,7 +8,7 @@ Same names, signatures, printed lines, return order and error behaviour as the r
 * ``get_observations(recordings, centroids)``                            (:82-120, HIP encoder)
 * ``safe_log`` / ``safe_exp`` / ``log_sum_exp``                          (:46-79)
 
-The EM iterations run in hand-written HIP kernels (hmm_training_amd/csrc/hmmbw.hip) through the C
+The EM iterations run in hand-written HIP kernels (hmm_training_amd/csrc/: hmmbw.hip and the units beside it) through the C
 ABI of include/hmmbw.h.  When ``torch.distributed`` is initialised with world_size > 1, every rank
 calls ``hmm_training`` with the same list, trains on its contiguous length-balanced shard, and
 all ranks return identical parameters (one RCCL all-reduce of the statistics per iteration).

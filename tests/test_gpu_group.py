@@ -105,6 +105,42 @@ def test_group_members_stop_at_their_own_iteration(oracle):
     assert len(set(its)) > 1, "fixture should stop the words at different iterations"
 
 
+def test_group_timing_counts_the_grouped_launches(oracle):
+    """hmmbw_group_timing: one event pair per grouped launch; the timed launches compute what the oracle
+    does in 5 iterations, and the group trains to the oracle's end afterwards."""
+    from hmm_training_amd.engine import BaumWelchEngine, EngineGroup
+    words = word_set(3, 4, 16, R=4, seed=5, tlo=8, thi=30)
+    engines = []
+    for obs, pi, A, B in words:
+        e = BaumWelchEngine(4, 16, device=0)
+        e.set_observations(obs)
+        e.set_params(pi, A, B)
+        engines.append(e)
+
+    def check(m, st, ref):
+        assert st.iterations == ref.iterations, f"word {m}"
+        p2, A2, B2 = engines[m].params(normalise=True)
+        assert_params(A2, ref.A, f"A[{m}]")
+        assert_params(B2, ref.B, f"B[{m}]")
+        assert_params(p2, ref.pi, f"pi[{m}]")
+
+    with EngineGroup(engines) as grp:
+        for e in engines:
+            e.reset(1e-6, 5)
+        grp.timing(1)
+        grp.enqueue_iterations(5)
+        ms, n = grp.timing(0)
+        print(f"group: {ms:.4f} ms / {n}")
+        assert n == 5 and ms > 0
+        for m, (obs, pi, A, B) in enumerate(words):
+            check(m, engines[m].status()[0], oracle_run(oracle, obs, 4, 16, 1e-6, 5, pi, A, B))
+            engines[m].set_params(pi, A, B)  # back to the warm start
+        sts = grp.train(1e-6, 200)
+    for m, (obs, pi, A, B) in enumerate(words):
+        check(m, sts[m], oracle_run(oracle, obs, 4, 16, 1e-6, 200, pi, A, B))
+        engines[m].close()
+
+
 @pytest.mark.parametrize("N,K,dense", [(8, 256, False), (8, 256, True), (5, 32, False), (16, 64, True)])
 def test_group_score_matches_oracle(oracle, N, K, dense):
     from hmm_training_amd.engine import BaumWelchEngine, EngineGroup

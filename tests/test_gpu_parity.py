@@ -342,6 +342,38 @@ def test_score_matrix_and_timing():
         assert n == 4 and ms > 0
 
 
+def test_timing_split_prices_the_estep_kernel_alone():
+    """hmmbw_timing_split: the wide path's timed launches carry an event between the E-step kernel and
+    k_bnum_gather; the small-N atomic path has no follow-up kernel, so nothing is split."""
+    from hmm_training_amd.engine import BaumWelchEngine
+    rng = np.random.default_rng(7)
+    _, pi, A, B = random_problem(rng, 20, 50, R=1, tmax=1, topology="left_to_right")
+    # 40 sequences: three 16-sequence tiles, the last one ragged
+    obs = [rng.integers(0, 50, size=int(t)) for t in rng.integers(10, 31, size=40)]
+    with BaumWelchEngine(20, 50) as eng:
+        eng.set_observations(obs)
+        eng.set_params(pi, A, B)
+        eng.timing(1)
+        eng.reset(0.0, 3)
+        eng.enqueue_iterations(3)
+        main_ms, n_main = eng.timing_split()
+        total_ms, n = eng.timing(0)
+        print(f"wide: main {main_ms:.4f} ms / {n_main}, total {total_ms:.4f} ms / {n}")
+        assert n == 3 and n_main == 3
+        assert 0 < main_ms <= total_ms
+    _, pi, A, B = random_problem(rng, 4, 16, R=1, tmax=1, topology="left_to_right")
+    obs = [rng.integers(0, 16, size=int(t)) for t in rng.integers(10, 31, size=40)]
+    with BaumWelchEngine(4, 16) as eng:
+        eng.set_observations(obs)
+        eng.set_params(pi, A, B)
+        eng.timing(1)
+        eng.reset(0.0, 3)
+        eng.enqueue_iterations(3)
+        main_ms, n_main = eng.timing_split()
+        total_ms, n = eng.timing(0)
+        assert n == 3 and n_main == 0 and main_ms == 0.0
+
+
 @pytest.mark.parametrize("N,topology", [(8, "left_to_right"), (8, "dense"), (40, "dense")])
 @pytest.mark.parametrize("equal_lengths", [True, False])
 def test_pathological_emissions_fall_back_to_safe_scaling(N, topology, equal_lengths, oracle):
