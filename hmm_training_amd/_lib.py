@@ -52,6 +52,7 @@ OPT_PEER_TIMEOUT_MS = 9
 OPT_LIVE_STATUS = 10
 OPT_WQ_TIMEOUT_MS = 11
 OPT_WIDE_WQ = 12
+OPT_LDS_LAYOUT = 13
 INFO_WIDE_WQ_ACTIVE = 101
 INFO_WAVES = 102
 INFO_WORKGROUPS = 103
@@ -61,6 +62,7 @@ INFO_EXTRA_WAVES = 106
 INFO_PEER_CHUNKS = 107
 INFO_JOINED = 108
 INFO_SPLIT_EXTRA = 109
+INFO_LDS_LAYOUT = 113
 ALLREDUCE = {"rccl": 0, "peer": 1}
 
 

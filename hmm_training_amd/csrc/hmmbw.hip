@@ -237,7 +237,7 @@ int check_closed(const hmmbw_ctx *c) {
 
 static void free_obs(hmmbw_ctx *c) {
     sync_ctx(c);
-    dfree(c->d_sym); dfree(c->d_wsym); dfree(c->d_wckoff); dfree(c->d_wspoff);
+    dfree(c->d_sym); dfree(c->d_sym2); dfree(c->d_wsym); dfree(c->d_wckoff); dfree(c->d_wspoff);
     dfree(c->d_wT); dfree(c->d_wfull); dfree(c->d_slen); dfree(c->d_sseq);
     dfree(c->d_ck); dfree(c->d_sp); dfree(c->d_ebuf); dfree(c->d_logp); dfree(c->d_llpart); dfree(c->d_zf);
     dfree(c->d_gam); dfree(c->d_bptr); dfree(c->d_brows); dfree(c->d_part); dfree(c->d_wq);
@@ -467,6 +467,27 @@ static bool joined_map(const hmmbw_ctx *c) {
            c->nblocks - c->nfull <= c->nfull && xw <= kBlock / kWave;
 }
 
+// The joined launch runs on the class-split LDS tables (k_estep_join<.., 1>, lds_layout.hpp).  The context keeps a
+// second pack set for it (d_sym2, row offsets of the 256-B rows): the scorer, the statistics pass off the joined
+// map, the grouped and the deterministic kernels keep d_sym, the row tables (64 KiB, two workgroups per CU) and
+// their code as it was.  HMMBW_OPT_LDS_LAYOUT / HMMBW_LDS_LAYOUT = 0 keeps the joined launch on the row tables too.
+// The second class's tables are 64 KB more LDS stores in every launch's prologue, +0.4 to +0.55 us whatever the
+// shape (T = 8 at 8,192 sequences 13.07 -> 13.64 us), against conflict-free emission reads in the sweeps, which
+// pay where a CU's LDS array is the busy resource: on the spread map's CUs with extra groups, in long sweeps.
+// Measured (profiles/r7/lds_layout_sweep.txt, us per iteration, row -> class-split tables): 10,000 sequences
+// T = 96 20.35 -> 20.63, 128 22.61 -> 22.81, 144 24.13 -> 23.96, 160 25.58 -> 25.32, 200 28.6 -> 28.0; 12,500
+// sequences T = 128 25.50 -> 25.32, 160 28.39 -> 27.90, 200 32.6 -> 31.7; without extra groups 8,192 x 200 27.05
+// -> 27.39; dense cfg3 (ds_read_b64 emissions, other lane groups) 58.8 -> 59.3.  So by default (-1): left-to-right,
+// extra groups, and a mean wave length of at least kSplitTablesMinSteps; 1 forces them wherever they can run.
+constexpr long long kSplitTablesMinSteps = 144;
+static bool split_tables_policy(const hmmbw_ctx *c, long long nblocks, long long nfull, long long steps, long long nwaves) {
+    return c->lds_layout == 1 || (c->lds_layout == -1 && nblocks > nfull && steps >= kSplitTablesMinSteps * nwaves);
+}
+static bool split_tables_map(const hmmbw_ctx *c) {
+    return c->split_tables() && c->d_sym2 && joined_map(c) &&
+           (c->lds_layout == 1 || c->topo == HMMBW_TOPOLOGY_LEFT_TO_RIGHT);
+}
+
 // The split extra waves run (estep_small_body SPLITOK, "split"): dense, and left-to-right on the joined map.
 static bool split_extra_map(const hmmbw_ctx *c) {
     const bool topo_ok = c->topo == HMMBW_TOPOLOGY_DENSE || (c->topo == HMMBW_TOPOLOGY_LEFT_TO_RIGHT && joined_map(c));
@@ -530,11 +551,16 @@ int plan_estep(hmmbw_ctx *c, bool fwd_only, const IterState *state, double *copi
                 p.nll = c->nfull;
                 p.block = 2 * kBlock;
                 p.lds = sizeof(double) * (tabs + (size_t)(2 * wpb) * c->G * NV + 16);  // + [8 waves][2] LL pairs
+                if (split_tables_map(c) && ks.join_estep_split) {  // the class-split tables and their packs
+                    p.fn = ks.join_estep_split;
+                    a.L.sym = c->d_sym2;
+                    p.lds = sizeof(double) * (c->split_table_doubles() + (size_t)(2 * wpb) * c->G * NV + 16);
+                }
             }
             // left-to-right: split extra waves on the joined map only (round 6, cfg3 29.63 -> 28.33 us,
             // profiles/r6/split_lr_ab.txt); beside separate extra workgroups they cost more than they save
             // (round 5: 34.0 -> 35.6 us)
-            if (lr && p.fn != ks.join_estep) a.split_extra = 0;
+            if (lr && p.block != 2 * kBlock) a.split_extra = 0;
             if (HMMBW_ZFULL && !lr && !fwd_only) {  // dense: the forward stores every z_t (hmmbw_device.hpp)
                 if (int rc = ensure_zf(c)) return rc;
                 a.ckpt = c->d_zf;
@@ -671,6 +697,7 @@ int hmmbw_ctx_create(int device, int n_states, int n_symbols, hmmbw_ctx **out) {
     c->NP = c->wide ? 16 * ((n_states + 15) / 16) : 0;
     c->G = c->wide ? c->NP : (n_states <= 2 ? 2 : n_states <= 4 ? 4 : n_states <= 8 ? 8 : 16);
     c->U = c->wide ? 16 : kWave / c->G;
+    if (const char *le = std::getenv("HMMBW_LDS_LAYOUT")) c->lds_layout = std::atoi(le) == 0 ? 0 : (std::atoi(le) == 1 ? 1 : -1);
     if (const char *we = std::getenv("HMMBW_WIDE_WQ")) c->wq_mode = std::atoi(we) == 0 ? 0 : (std::atoi(we) == 1 ? 1 : -1);
     int rc = set_device(c);
     if (!rc) {
@@ -889,6 +916,9 @@ int hmmbw_set_observations(hmmbw_ctx *c, const int64_t *offsets, const int32_t *
         }
     }
     int rc = dalloc(&c->d_sym, (size_t)std::max(symtot, 1LL));
+    // (symtot / U: the waves' steps, each wave's rounded up to whole chunks)
+    const bool sym2 = c->split_tables() && split_tables_policy(c, nblocks, nfull, symtot / U, nwaves);
+    if (!rc && sym2) rc = dalloc(&c->d_sym2, (size_t)std::max(symtot, 1LL));
     if (!rc) rc = dalloc(&c->d_wsym, (size_t)nwaves);
     if (!rc) rc = dalloc(&c->d_wckoff, (size_t)nwaves);
     if (!rc) rc = dalloc(&c->d_wspoff, (size_t)nwaves);
@@ -954,6 +984,11 @@ int hmmbw_set_observations(hmmbw_ctx *c, const int64_t *offsets, const int32_t *
     if (!rc) rc = dalloc(&c->d_llpart, 4 * (size_t)std::max(nblocks, 1LL));
     if (rc) return rc;
     HIP_TRY(hipMemcpy(c->d_sym, hsym.data(), sizeof(uint16_t) * hsym.size(), hipMemcpyHostToDevice));
+    if (sym2) {  // the class-split rows are twice as long: o * row_bytes -> o * lay2_row_bytes (<= 65,280)
+        static_assert(lay2_row_bytes(8) == 2 * 8 * 16, "class-split row stride");
+        for (uint16_t &e : hsym) e = (uint16_t)(e / row_bytes * lay2_row_bytes(c->G));
+        HIP_TRY(hipMemcpy(c->d_sym2, hsym.data(), sizeof(uint16_t) * hsym.size(), hipMemcpyHostToDevice));
+    }
     if (c->wide || c->det) {
         HIP_TRY(hipMemcpy(c->d_bptr, bptr.data(), sizeof(long long) * bptr.size(), hipMemcpyHostToDevice));
         HIP_TRY(hipMemcpy(c->d_brows, brows.data(), sizeof(unsigned) * brows.size(), hipMemcpyHostToDevice));
@@ -1006,6 +1041,13 @@ int hmmbw_set_option(hmmbw_ctx *c, int key, int64_t value) {
         if (value != 0 && !c->wide && !c->lds_tables())
             return fail(HMMBW_E_UNSUPPORTED, "deterministic mode needs the LDS emission tables (N <= 16) or the wide path");
         c->det = value != 0;
+        return HMMBW_OK;
+    }
+    if (key == HMMBW_OPT_LDS_LAYOUT) {
+        if (value < -1 || value > 1)
+            return fail(HMMBW_E_INVALID, "HMMBW_OPT_LDS_LAYOUT: -1 (auto), 0 (row tables) or 1 (class-split)");
+        if (c->has_obs) return fail(HMMBW_E_STATE, "set the LDS table layout before hmmbw_set_observations");
+        c->lds_layout = (int)value;
         return HMMBW_OK;
     }
     if (key == HMMBW_OPT_MERGE_MSTEP) {
@@ -1076,6 +1118,8 @@ int hmmbw_get_option(const hmmbw_ctx *c, int key, int64_t *value) {
         case HMMBW_OPT_LIVE_STATUS: *value = c->h_live ? 1 : 0; return HMMBW_OK;
         case HMMBW_OPT_WQ_TIMEOUT_MS: *value = c->wq_timeout_ms; return HMMBW_OK;
         case HMMBW_OPT_WIDE_WQ: *value = c->wq_mode; return HMMBW_OK;
+        case HMMBW_OPT_LDS_LAYOUT: *value = c->lds_layout; return HMMBW_OK;
+        case HMMBW_INFO_LDS_LAYOUT: *value = c->has_obs && split_tables_map(c) ? 1 : 0; return HMMBW_OK;
         case HMMBW_INFO_WIDE_WQ_ACTIVE: *value = c->d_wq ? 1 : 0; return HMMBW_OK;
         case HMMBW_INFO_WAVES: *value = c->wide ? c->nblocks * (c->NP / 16) : c->nwaves; return HMMBW_OK;
         case HMMBW_INFO_WORKGROUPS: *value = c->d_wq ? c->wq_grid : c->nblocks; return HMMBW_OK;

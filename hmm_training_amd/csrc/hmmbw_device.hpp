@@ -15,6 +15,8 @@
 #include <type_traits>
 #include <vector>
 
+#include "lds_layout.hpp"
+
 #include "../../include/hmmbw.h"
 
 namespace hmmbw {
@@ -504,6 +506,8 @@ constexpr int kHistOff = kTabPad ? 40960 : 32768;
 __host__ __device__ constexpr bool lds_tables_fit(int K, int GP) { return (size_t)K * GP * 16 <= (size_t)kHistOff; }
 __host__ __device__ constexpr size_t lds_table_bytes(int K, int GP) { return (size_t)kHistOff + (size_t)K * GP * 16; }
 
+// (the class-split layout, LAY = 1, of the joined map's G = 8 kernels: lds_layout.hpp)
+
 // Entry i = k * GP + c (symbol k, state column c) of the LDS emission tables, 16 B each:
 // P {a_cc b_c(k), a_{c-1,c} b_c(k)} (left-to-right, PT) or {b_c(k), 0} (dense); H {histogram, b_c(k)}.
 // Round 4 measured two alternatives, both reverted: a dense layout with two 8-B copies of b per row (one
@@ -511,13 +515,25 @@ __host__ __device__ constexpr size_t lds_table_bytes(int K, int GP) { return (si
 // against 73.4), and H entries {h, h'} with the even / odd sequence slots adding into their own half (a
 // ds_add_f64 serves 16 contiguous lanes = two slots x 8 states, and both slots' adds otherwise hit the same
 // 8 even banks), b(o_0) then coming from the statistics: LR cfg3 36.96-36.98 us against 35.23-35.58.
-template <bool PT, int GP>
+// LAY = 1, the class-split layout: both classes' copies of the entry (see lay2_p_off).
+template <bool PT, int GP, int LAY = 0>
 __device__ __forceinline__ void tab_put(double *sP, double *sH, int i, double px, double py, double b) {
-    reinterpret_cast<double2 *>(sP)[i] = PT ? double2{px, py} : double2{b, 0.0};
-    reinterpret_cast<double2 *>(sH)[i] = double2{0.0, b};
+    const double2 p = PT ? double2{px, py} : double2{b, 0.0};
+    if constexpr (LAY == 0) {
+        reinterpret_cast<double2 *>(sP)[i] = p;
+        reinterpret_cast<double2 *>(sH)[i] = double2{0.0, b};
+    } else {
+        const int k = i / GP, c = i - k * GP;
+        char *e = reinterpret_cast<char *>(sP) + lay2_p_off(GP, 0, k, c);
+#pragma unroll
+        for (int cls = 0; cls < 2; ++cls) {
+            *reinterpret_cast<double2 *>(e + cls * lay2_class_off(GP)) = p;
+            *reinterpret_cast<double2 *>(e + cls * lay2_class_off(GP) + lay2_hist_off(GP)) = double2{0.0, b};
+        }
+    }
 }
 
-template <int N, int G, int GP, bool PT, int BLK = kBlock>
+template <int N, int G, int GP, bool PT, int BLK = kBlock, int LAY = 0>
 __device__ __forceinline__ bool merged_mstep(const EArgs &a, double *sP, double *sH, double *sPA, long long bid);
 __device__ __forceinline__ int rank_ll_count(const EArgs &a);
 __device__ __forceinline__ void rank_ll_fold(const EArgs &a, long long nblk);
@@ -533,11 +549,16 @@ __device__ __forceinline__ void ll_merge(double &M, double &S, double m2, double
 // BLK = 2 kBlock (k_estep_join, left-to-right E-step): the spread map's extra workgroup bid runs as waves
 // 4.. of full workgroup bid (one 8-wave workgroup per CU), so each CU builds one set of LDS tables, runs
 // one M-step prologue and flushes one histogram.
-template <int N, int G, bool LR, bool LDSTAB, bool FWD_ONLY, bool DET = false, int BLK = kBlock>
+// LAY = 1 (joined map, G = 8): the class-split LDS tables (lay2_p_off) and their packs (Layout::sym then holds
+// the row offsets o 2 GP 16).
+template <int N, int G, bool LR, bool LDSTAB, bool FWD_ONLY, bool DET = false, int BLK = kBlock, int LAY = 0>
 __device__ __forceinline__ void estep_small_body(const EArgs &a, const long long bid, const long long nblk) {
     static_assert(!DET || (LDSTAB && !FWD_ONLY), "deterministic mode: E-step with LDS tables");
     constexpr bool JOIN = BLK > kBlock;
     static_assert(!JOIN || (BLK == 2 * kBlock && LDSTAB && !FWD_ONLY && !DET), "joined map: E-step with LDS tables");
+    static_assert(LAY == 0 || (LAY == 1 && JOIN && G == 8 && kTabPad == 0), "class-split tables: joined map, G = 8");
+    // H entry - P entry of a lane's step address: the immediate offset of the histogram add and the H.b read
+    constexpr int HOFF = LAY ? lay2_hist_off(G) : kHistOff;
     constexpr int U = kWave / G;
     // dense G = 8: xi on the 4x4x4 MFMA (xi_mfma8), two accumulators per lane in its D layout
     constexpr bool XM = !LR && G == 8 && !FWD_ONLY && HMMBW_XI_MFMA;
@@ -576,7 +597,7 @@ __device__ __forceinline__ void estep_small_body(const EArgs &a, const long long
     const int K = a.K;
     double *sP = smem;                   // LDSTAB: P-table [K][GP] {x, y} (see kHistOff)
     double *sH = smem + kHistOff / 8;    // LDSTAB: H-table [K][GP] {h, b}
-    double *sRed = smem + (LDSTAB ? lds_table_bytes(K, GP) / 8 : 0);  // [waves][G][NV] + ll scratch
+    double *sRed = smem + (LDSTAB ? (LAY ? lay2_table_bytes(K, GP) : lds_table_bytes(K, GP)) / 8 : 0);  // [waves][G][NV] + ll scratch
     bool merged = false;
     if constexpr (LDSTAB && !FWD_ONLY) merged = a.merged != 0;
     const int wpb = JOIN ? kBlock / kWave : blockDim.x >> 6;  // waves of a full (sequence-group) workgroup
@@ -595,7 +616,7 @@ __device__ __forceinline__ void estep_small_body(const EArgs &a, const long long
         // the previous iteration's M-step, computed redundantly by every workgroup straight into
         // its LDS tables (no separate M-step kernel, no parameter round trip through HBM)
         if constexpr (LDSTAB && !FWD_ONLY)
-            if (!merged_mstep<N, G, GP, PT, BLK>(a, sP, sH, sPA, bid)) return;  // done or stopped (:346)
+            if (!merged_mstep<N, G, GP, PT, BLK, LAY>(a, sP, sH, sPA, bid)) return;  // done or stopped (:346)
     } else {
         if (a.state != nullptr && a.state->done) return;  // converged: device-side no-op
         if (tid < G) sPA[tid] = tid < N ? a.pi[tid] : 0.0;
@@ -623,9 +644,9 @@ __device__ __forceinline__ void estep_small_body(const EArgs &a, const long long
                             const int c = i % GP;
                             const double ad = c < N ? sPA[G + c * N + c] : 0.0;
                             const double ai = (c >= 1 && c < N) ? sPA[G + (c - 1) * N + c] : 0.0;
-                            tab_put<PT, GP>(sP, sH, i, ad * x[q], ai * x[q], x[q]);
+                            tab_put<PT, GP, LAY>(sP, sH, i, ad * x[q], ai * x[q], x[q]);
                         } else {
-                            tab_put<PT, GP>(sP, sH, i, 0.0, 0.0, x[q]);
+                            tab_put<PT, GP, LAY>(sP, sH, i, 0.0, 0.0, x[q]);
                         }
                     }
                 }
@@ -691,7 +712,8 @@ __device__ __forceinline__ void estep_small_body(const EArgs &a, const long long
         };
         // This lane's P-table entry for packed entry k.  With LDS tables the packs hold the byte
         // offset of the symbol's row (o * GP * 16, precomputed on the host), else the symbol.
-        char *pj = reinterpret_cast<char *>(sP) + j * 16;
+        // (class-split tables: the slot's class region, once per wave)
+        char *pj = reinterpret_cast<char *>(sP) + j * 16 + (LAY ? lay2_class(u) * lay2_class_off(GP) : 0);
         auto pent = [&](const uint4 &p, int k) -> char * { return pj + sym_of(p, k); };
         auto brow = [&](const uint4 &p, int k) -> const double * {  // b_j(o) (and b_{j+1}(o) after it, global)
             if constexpr (LDSTAB) return reinterpret_cast<const double *>(pent(p, k));
@@ -821,7 +843,7 @@ __device__ __forceinline__ void estep_small_body(const EArgs &a, const long long
 #pragma unroll
             for (int i = 0; i < 4; ++i) Q[i] = loadpack(i < nch ? i : nch - 1);
             double b00;  // b_j(o_0) for pi_j b_j(o_0) (:357-360)
-            if constexpr (PT) b00 = *reinterpret_cast<const double *>(pent(Q[0], 0) + kHistOff + 8);  // H.b
+            if constexpr (PT) b00 = *reinterpret_cast<const double *>(pent(Q[0], 0) + HOFF + 8);  // H.b
             else b00 = *brow(Q[0], 0);
             Em E[2][kChunk];
 #pragma unroll
@@ -1202,7 +1224,7 @@ __device__ __forceinline__ void estep_small_body(const EArgs &a, const long long
                         // columns), so the compiler's lgkmcnt bookkeeping stays exact
 #pragma unroll
                         for (int k = 0; k < kChunk; ++k)  // :474-485
-                            atomicAdd(reinterpret_cast<double *>(lds_ptr(hac[k]) + kHistOff), gk[k]);  // H.h of o_t
+                            atomicAdd(reinterpret_cast<double *>(lds_ptr(hac[k]) + HOFF), gk[k]);  // H.h of o_t
                     } else if (N == G || jv) {
 #pragma unroll
                         for (int k = 0; k < kChunk; ++k)
@@ -1321,7 +1343,13 @@ __device__ __forceinline__ void estep_small_body(const EArgs &a, const long long
         for (int idx = tid; idx < K * G; idx += blockDim.x) {
             const int k = idx / G, jj = idx - k * G;
             if (jj >= N) continue;
-            const double x = sH[((size_t)k * GP + jj) * 2];
+            double x;
+            if constexpr (LAY) {  // the two classes' histograms of (k, jj)
+                const char *h = reinterpret_cast<const char *>(smem) + lay2_p_off(GP, 0, k, jj) + HOFF;
+                x = *reinterpret_cast<const double *>(h) + *reinterpret_cast<const double *>(h + lay2_class_off(GP));
+            } else {
+                x = sH[((size_t)k * GP + jj) * 2];
+            }
             if (x != 0.0) unsafeAtomicAdd(&accb[a.off_bnum + (long long)k * N + jj], x);
         }
     }
@@ -1454,12 +1482,12 @@ __global__ void __launch_bounds__(kBlock, 2) k_estep_small(EArgs a) {  // 2 wave
 // Joined spread map (E-step with LDS tables): one 8-wave workgroup per CU, grid = nfull; waves 4.. of
 // workgroup b run extra workgroup b's xact sequence groups (estep_small_body, JOIN), and on the dense path
 // their split B partners (hand-over by LDS flag).
-template <int N, int G, bool LR>
+template <int N, int G, bool LR, int LAY = 0>
 __global__ void __launch_bounds__(2 * kBlock, 1) k_estep_join(EArgs a) {
 #if HMMBW_KARG_TOUCH
     touch_kernargs<EArgs>();
 #endif
-    estep_small_body<N, G, LR, true, false, false, 2 * kBlock>(a, blockIdx.x, gridDim.x);
+    estep_small_body<N, G, LR, true, false, false, 2 * kBlock, LAY>(a, blockIdx.x, gridDim.x);
 }
 
 // Grouped launch: g.nm models of one shape (same N, topology and tables), model m owning workgroups
@@ -1868,7 +1896,7 @@ __device__ __forceinline__ void rank_ll_fold(const EArgs &a, long long nblk) {  
     }
 }
 
-template <int N, int G, int GP, bool PT, int BLK>
+template <int N, int G, int GP, bool PT, int BLK, int LAY>
 __device__ __forceinline__ bool merged_mstep(const EArgs &a, double *sP, double *sH, double *sPA, long long bid) {
     constexpr int NSM = N + N * N + 2 * N;  // pi_num, xi, gamma_den_excl, gamma_den_all
     constexpr int NW = BLK / 64;
@@ -2005,9 +2033,9 @@ __device__ __forceinline__ bool merged_mstep(const EArgs &a, double *sP, double 
             if constexpr (PT) {
                 const double ad = kSameState ? ad0 : a_of(jj, jj);
                 const double ai = kSameState ? ai0 : (jj >= 1 ? a_of(jj - 1, jj) : 0.0);
-                tab_put<PT, GP>(sP, sH, i, ad * bval[q], ai * bval[q], bval[q]);  // histogram zeroed, b
+                tab_put<PT, GP, LAY>(sP, sH, i, ad * bval[q], ai * bval[q], bval[q]);  // histogram zeroed, b
             } else {
-                tab_put<PT, GP>(sP, sH, i, 0.0, 0.0, bval[q]);
+                tab_put<PT, GP, LAY>(sP, sH, i, 0.0, 0.0, bval[q]);
             }
         }
     }
@@ -2027,7 +2055,7 @@ __device__ __forceinline__ bool merged_mstep(const EArgs &a, double *sP, double 
     if constexpr (GP > N) {
         for (int i = tid; i < K * (GP - N); i += BLK) {
             const int k = i / (GP - N), c = N + (i - k * (GP - N));
-            tab_put<PT, GP>(sP, sH, k * GP + c, 0.0, 0.0, 0.0);
+            tab_put<PT, GP, LAY>(sP, sH, k * GP + c, 0.0, 0.0, 0.0);
         }
     }
     __syncthreads();

@@ -19,6 +19,7 @@ struct Kernels {
     GroupFn group_estep = nullptr, group_score = nullptr;  // grouped launches (LDS tables only)
     KernelFn det_estep = nullptr;                          // deterministic-reduction E-step (LDS tables, wide)
     KernelFn join_estep = nullptr;                         // joined spread map (left-to-right, LDS tables)
+    KernelFn join_estep_split = nullptr;                   // the same on the class-split LDS tables (G = 8; lay2_p_off)
 };
 
 // E-step and scorer kernels for N states (1 <= N <= 16), left-to-right or dense, with or without the

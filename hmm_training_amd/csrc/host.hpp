@@ -135,9 +135,13 @@ struct hmmbw_ctx {
     int split_extra = 1;          // EArgs::split_extra (HMMBW_SPLIT_EXTRA=0 turns it off)
     int join = 1;                 // left-to-right E-step on the joined spread map (k_estep_join; HMMBW_JOIN=0 off)
     int join_dense = 1;           // the dense E-step on it too (HMMBW_JOIN_DENSE=0 off)
+    int lds_layout = -1;          // HMMBW_OPT_LDS_LAYOUT: the joined map on the class-split LDS tables (G = 8):
+                                  // -1 where they pay (hmmbw.hip, split_tables_map), 0 never, 1 wherever they can run
     bool fits_cus = false;        // the launch map's workgroups fit one per CU (set_observations)
     long long last_nll = 0;       // per-workgroup log-likelihood pairs written by the last E-step launch
     uint16_t *d_sym = nullptr;
+    uint16_t *d_sym2 = nullptr;   // the packs of the class-split tables (row offsets o 2 G 16), or nullptr: the
+                                  // joined kernel alone reads them; every other kernel keeps d_sym and its layout
     long long *d_wsym = nullptr, *d_wckoff = nullptr, *d_wspoff = nullptr;
     int *d_wT = nullptr, *d_wfull = nullptr, *d_slen = nullptr, *d_sseq = nullptr;
     double *d_ck = nullptr, *d_logp = nullptr, *d_llpart = nullptr;  // llpart: [2][nblocks][2]
@@ -221,6 +225,12 @@ struct hmmbw_ctx {
     bool lds_tables() const { return !wide && lds_tables_fit(K, G + kTabPad); }
     // LDS doubles of the small kernels' tables
     size_t lds_table_doubles() const { return lds_tables() ? lds_table_bytes(K, G + kTabPad) / sizeof(double) : 0; }
+    // the class-split tables (lds_layout.hpp, lay2_p_off) can serve this context's joined launches: G = 8,
+    // the rows of one class within 64 KiB (uint16 packs); both classes then fit the CU's 160 KiB with the scratch
+    bool split_tables() const {
+        return lds_layout != 0 && !wide && !det && kTabPad == 0 && G == 8 && lds_tables() && lay2_tables_fit(K, G);
+    }
+    size_t split_table_doubles() const { return lay2_table_bytes(K, G) / sizeof(double); }
     bool can_merge() const { return merge_mstep && lds_tables() && copy_len() <= kMergedMaxStats && nwaves > 0; }
     // statistics copies in the fused all-reduce buffer: the wide path's B numerator is written once (by
     // k_bnum_gather, into copy 0), and its tiles finish at different times, so its atomics need no

@@ -314,7 +314,16 @@ class BaumWelchEngine:
                 "waves_per_workgroup": self.get_option(INFO_WAVES_PER_WORKGROUP),
                 "full_workgroups": self.get_option(INFO_FULL_WORKGROUPS),
                 "extra_waves": self.get_option(INFO_EXTRA_WAVES), "work_queue": self.work_queue_active,
-                "joined": self.get_option(INFO_JOINED) == 1, "split_extra": self.get_option(INFO_SPLIT_EXTRA) == 1}
+                "joined": self.get_option(INFO_JOINED) == 1, "split_extra": self.get_option(INFO_SPLIT_EXTRA) == 1,
+                "lds_layout": self.lds_layout}
+
+    @property
+    def lds_layout(self) -> int:
+        """HMMBW_INFO_LDS_LAYOUT: 1 if the E-step launch runs on the class-split LDS emission tables (joined
+        map, N = 5..8), 0 on the row tables (also what a library from before the key runs)."""
+        from ._lib import INFO_LDS_LAYOUT
+        v = ctypes.c_int64()
+        return v.value if self._lib.hmmbw_get_option(self._ctx, INFO_LDS_LAYOUT, ctypes.byref(v)) == 0 else 0
 
     def peer_chunks(self) -> int:
         """Chunks of the peer all-reduce payload (one flag per (rank, chunk) per iteration), 0 without a region."""

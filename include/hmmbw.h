@@ -35,7 +35,9 @@ extern "C" {
 #define HMMBW_ABI_VERSION 5 /* 2: hmmbw_iterate_begin/_end, status snapshots, comm info/payload;
                               3: peer all-reduce (hmmbw_peer_*), HMMBW_E_TIMEOUT, cache trim, split timing;
                               4: live status mirror (HMMBW_OPT_LIVE_STATUS, hmmbw_status_live_wait);
-                              5: hmmbw_get_option, HMMBW_OPT_WQ_TIMEOUT_MS, HMMBW_OPT_WIDE_WQ */
+                              5: hmmbw_get_option, HMMBW_OPT_WQ_TIMEOUT_MS, HMMBW_OPT_WIDE_WQ
+                                 (HMMBW_OPT_LDS_LAYOUT / HMMBW_INFO_LDS_LAYOUT are new keys of the same calls:
+                                 an older library answers them HMMBW_E_INVALID, no entry point changed) */
 
 #define HMMBW_OK 0
 #define HMMBW_E_INVALID (-1)        /* bad argument (shape, range, null pointer)             */
@@ -276,6 +278,13 @@ int hmmbw_score(hmmbw_ctx *ctx, double *out);
  * tiles exceed 4 per CU, 1 whenever they exceed the CU count, 0 never.  The environment variable
  * HMMBW_WIDE_WQ=0/1 sets a new context's default.  Takes effect at once. */
 #define HMMBW_OPT_WIDE_WQ 12
+/* LDS emission-table layout of the joined map's E-step (N = 5..8, at most 256 symbols): the class-split tables,
+ * whose emission reads are free of bank conflicts at the price of a larger table build per launch, or the row
+ * tables every other kernel uses.  -1 (default): class-split where it measured faster (left-to-right, more
+ * sequence groups than SIMDs, a mean of at least 144 steps per group); 0: never; 1: wherever the joined map
+ * runs.  HMMBW_INFO_LDS_LAYOUT says what a launch uses.  The environment variable HMMBW_LDS_LAYOUT=-1/0/1 sets
+ * a new context's default.  Set it before hmmbw_set_observations (the observations are packed for the layout). */
+#define HMMBW_OPT_LDS_LAYOUT 13
 int hmmbw_set_option(hmmbw_ctx *ctx, int key, int64_t value);
 /* The current value of an option above, or a read-only fact about the loaded observations' E-step launch:
  * HMMBW_INFO_WIDE_WQ_ACTIVE    1 if it runs on the wide work queue;
@@ -294,7 +303,9 @@ int hmmbw_set_option(hmmbw_ctx *ctx, int key, int64_t value);
  *                              waves run as waves 4.. of full workgroup b, one 8-wave workgroup per CU, so
  *                              HMMBW_INFO_FULL_WORKGROUPS workgroups are launched (HMMBW_JOIN=0 turns it off);
  * HMMBW_INFO_SPLIT_EXTRA       1 if the extra workgroups' idle waves run the lower backward half of their
- *                              sequence groups (dense split; HMMBW_SPLIT_EXTRA=0 turns it off).
+ *                              sequence groups (dense split; HMMBW_SPLIT_EXTRA=0 turns it off);
+ * HMMBW_INFO_LDS_LAYOUT        LDS emission-table layout of the E-step launch: 1 the class-split tables (joined
+ *                              map, N = 5..8, K <= 256, see HMMBW_OPT_LDS_LAYOUT), 0 the row tables (or none).
  * (bench.py's roofline bounds price the busiest CU and SIMD from this map.) */
 #define HMMBW_INFO_WIDE_WQ_ACTIVE 101
 #define HMMBW_INFO_WAVES 102
@@ -312,6 +323,7 @@ int hmmbw_set_option(hmmbw_ctx *ctx, int key, int64_t value);
  * loads did not read back what was written (see hmmbw.hip, peer_region_alloc) */
 #define HMMBW_INFO_PEER_REGIONS_VALIDATED 111
 #define HMMBW_INFO_PEER_REGIONS_REJECTED 112
+#define HMMBW_INFO_LDS_LAYOUT 113
 int hmmbw_get_option(const hmmbw_ctx *ctx, int key, int64_t *value);
 
 /* E-step kernel timing with HIP events on the context stream (for bench/roofline).  Returns the

@@ -120,5 +120,20 @@ def steady_loops(path, name, steps_per_trip=32):
     return out
 
 
-if __name__ == "__main__" and False:
-    pass
+def addressing(path, name):
+    """How one small E-step kernel addresses its LDS tables: counts of the per-step address instruction
+    (v_add_u32_sdwa: lane base + uint16 pack entry), of the emission reads and of the histogram adds and 8-byte reads
+    by immediate offset."""
+    lines = open(path).read().splitlines()
+    start = next(i for i, l in enumerate(lines) if re.match(r"^_Z\S*" + re.escape(name) + r"\S*:", l))
+    end = next(i for i in range(start + 1, len(lines)) if lines[i].startswith(".Lfunc_end"))
+    c = Counter()
+    for l in lines[start:end]:
+        s = l.strip()
+        op = s.split()[0] if s else ""
+        if op == "v_add_u32_sdwa":
+            c[op] += 1
+        elif op in ("ds_read_b128", "ds_add_f64"):
+            m = re.search(r"offset:(\d+)", s)
+            c[f"{op} offset:{m.group(1) if m else 0}"] += 1
+    return dict(sorted(c.items()))
