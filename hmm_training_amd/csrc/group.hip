@@ -175,7 +175,7 @@ int hmmbw_group_iterate(hmmbw_group *g, int64_t n_iter) {
                     if (p.flip) c->scur ^= 1;  // slots are read by the launch through the plan's pointers
                     // a grouped kernel exists only outside the deterministic mode and never runs the joined
                     // map (allow_join = false above): ncopies sources, a pair per workgroup
-                    pend_local(c, e, c->nblocks);
+                    pend_local(c, e, c->map.nblocks);
                 }
             if (step == nl) {
                 if (int rc = group_launch(g, plans, nl, true)) return rc;

@@ -230,6 +230,13 @@ long long ms_to_ticks(const hmmbw_ctx *c, long long ms) {
     return ms > LLONG_MAX / khz ? LLONG_MAX : ms * khz;
 }
 
+// an integer from the environment: *v is written, and true returned, only if the variable is set
+static bool env_int(const char *name, int *v) {
+    const char *e = std::getenv(name);
+    if (e) *v = std::atoi(e);
+    return e != nullptr;
+}
+
 int check_closed(const hmmbw_ctx *c) {
     if (c->ar_open) return fail(HMMBW_E_STATE, "an iteration is open (hmmbw_iterate_end first)");
     return HMMBW_OK;
@@ -283,10 +290,9 @@ static EArgs make_eargs(hmmbw_ctx *c) {
     a.off_gex = c->off_gex();
     a.off_gall = c->off_gall();
     a.off_bnum = c->off_bnum();
-    a.nfull = c->nfull;
-    a.xact = c->xact;
+    a.nfull = c->map.nfull;
+    a.xact = c->map.xact;
     a.prio = c->prio >= 0 ? c->prio : (c->topo == HMMBW_TOPOLOGY_LEFT_TO_RIGHT ? 2 : 0);
-    a.split_extra = c->split_extra;
     return a;
 }
 
@@ -428,71 +434,21 @@ static int ensure_zf(hmmbw_ctx *c) {
 // to match the current observations; the counters and flags start cleared.
 static int ensure_wq(hmmbw_ctx *c) {
     bool want = false;
-    if (c->has_obs && c->wide && !c->det && c->nblocks < (1LL << 30)) {
-        int ncu = 0;
-        (void)hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, c->device);
-        if (ncu > 0 && c->wq_mode != 0) want = c->nblocks > (c->wq_mode == 1 ? ncu : 4LL * ncu);
+    if (c->has_obs && c->wide && !c->det && c->map.nblocks < (1LL << 30)) {
+        const int ncu = c->map.ncu;  // the device's CU count (set_observations)
+        if (ncu > 0 && c->wq_mode != 0) want = c->map.nblocks > (c->wq_mode == 1 ? ncu : 4LL * ncu);
     }
-    if (c->d_wq && (!want || c->wq_grid != 2 * c->nblocks)) {
+    if (c->d_wq && (!want || c->wq_grid != 2 * c->map.nblocks)) {
         sync_ctx(c);
         dfree(c->d_wq);
         c->wq_grid = 0;
     }
     if (want && !c->d_wq) {
-        if (int rc = dalloc(&c->d_wq, (size_t)c->nblocks + 2)) return rc;
-        HIP_TRY(hipMemset(c->d_wq, 0, sizeof(unsigned) * ((size_t)c->nblocks + 2)));
-        c->wq_grid = 2 * c->nblocks;
+        if (int rc = dalloc(&c->d_wq, (size_t)c->map.nblocks + 2)) return rc;
+        HIP_TRY(hipMemset(c->d_wq, 0, sizeof(unsigned) * ((size_t)c->map.nblocks + 2)));
+        c->wq_grid = 2 * c->map.nblocks;
     }
     return HMMBW_OK;
-}
-
-// The left-to-right E-step runs the joined spread map (k_estep_join): every extra workgroup of the spread map
-// (at most one per CU) becomes waves 4.. of the full workgroup with its index, so each CU runs one 8-wave
-// workgroup: one M-step prologue, one set of LDS tables and one histogram flush instead of two on the CUs
-// that host an extra workgroup.  cfg3: 32.2 -> 30.9 us per iteration (profiles/r5/join_ab.txt).
-// Round 6: the dense E-step joins too (HMMBW_JOIN_DENSE=0 keeps its separate extra workgroups); its split B
-// waves take A's hand-over through an LDS flag, so the joined workgroup's full waves are never held.
-#ifndef HMMBW_JOIN_ALL
-#define HMMBW_JOIN_ALL 1
-#endif
-static bool joined_map(const hmmbw_ctx *c) {
-    const bool topo_ok = c->topo == HMMBW_TOPOLOGY_LEFT_TO_RIGHT || (c->topo == HMMBW_TOPOLOGY_DENSE && c->join_dense);
-    const int xw = (c->topo == HMMBW_TOPOLOGY_DENSE && c->split_extra && 2 * c->xact <= kBlock / kWave) ? 2 * c->xact
-                                                                                                     : c->xact;
-    // Round 6: left-to-right without extra groups too (at most 4 groups per CU, one workgroup per CU), the idle waves
-    // 4-7 then only sharing the prologue's table build and the flush: T = 8 at 8,192 sequences 13.51 -> 12.96 us,
-    // 8,192 x 200 27.59 -> 27.32, 4,096 x 200 24.30 -> 23.72 (profiles/r6/join_all_ab.txt)
-    const bool all = HMMBW_JOIN_ALL && c->topo == HMMBW_TOPOLOGY_LEFT_TO_RIGHT && c->nblocks == c->nfull && c->fits_cus;
-    return c->join && topo_ok && !c->wide && !c->det && c->lds_tables() && (c->nblocks > c->nfull || all) &&
-           c->nblocks - c->nfull <= c->nfull && xw <= kBlock / kWave;
-}
-
-// The joined launch runs on the class-split LDS tables (k_estep_join<.., 1>, lds_layout.hpp).  The context keeps a
-// second pack set for it (d_sym2, row offsets of the 256-B rows): the scorer, the statistics pass off the joined
-// map, the grouped and the deterministic kernels keep d_sym, the row tables (64 KiB, two workgroups per CU) and
-// their code as it was.  HMMBW_OPT_LDS_LAYOUT / HMMBW_LDS_LAYOUT = 0 keeps the joined launch on the row tables too.
-// The second class's tables are 64 KB more LDS stores in every launch's prologue, +0.4 to +0.55 us whatever the
-// shape (T = 8 at 8,192 sequences 13.07 -> 13.64 us), against conflict-free emission reads in the sweeps, which
-// pay where a CU's LDS array is the busy resource: on the spread map's CUs with extra groups, in long sweeps.
-// Measured (profiles/r7/lds_layout_sweep.txt, us per iteration, row -> class-split tables): 10,000 sequences
-// T = 96 20.35 -> 20.63, 128 22.61 -> 22.81, 144 24.13 -> 23.96, 160 25.58 -> 25.32, 200 28.6 -> 28.0; 12,500
-// sequences T = 128 25.50 -> 25.32, 160 28.39 -> 27.90, 200 32.6 -> 31.7; without extra groups 8,192 x 200 27.05
-// -> 27.39; dense cfg3 (ds_read_b64 emissions, other lane groups) 58.8 -> 59.3.  So by default (-1): left-to-right,
-// extra groups, and a mean wave length of at least kSplitTablesMinSteps; 1 forces them wherever they can run.
-constexpr long long kSplitTablesMinSteps = 144;
-static bool split_tables_policy(const hmmbw_ctx *c, long long nblocks, long long nfull, long long steps, long long nwaves) {
-    return c->lds_layout == 1 || (c->lds_layout == -1 && nblocks > nfull && steps >= kSplitTablesMinSteps * nwaves);
-}
-static bool split_tables_map(const hmmbw_ctx *c) {
-    return c->split_tables() && c->d_sym2 && joined_map(c) &&
-           (c->lds_layout == 1 || c->topo == HMMBW_TOPOLOGY_LEFT_TO_RIGHT);
-}
-
-// The split extra waves run (estep_small_body SPLITOK, "split"): dense, and left-to-right on the joined map.
-static bool split_extra_map(const hmmbw_ctx *c) {
-    const bool topo_ok = c->topo == HMMBW_TOPOLOGY_DENSE || (c->topo == HMMBW_TOPOLOGY_LEFT_TO_RIGHT && joined_map(c));
-    return c->split_extra && !c->wide && !c->det && topo_ok && c->lds_tables() && c->nblocks > c->nfull &&
-           2 * c->xact <= kBlock / kWave;
 }
 
 // E-step launch e accumulates into copies and llpart; it clears `zero` (zero_len doubles) and, when
@@ -512,8 +468,8 @@ int plan_estep(hmmbw_ctx *c, bool fwd_only, const IterState *state, double *copi
     a.rank_ll = rank_ll;
     a.done_ctr = c->d_ctr;
     const int wpb = kBlock / kWave;
-    p.grid = (unsigned)c->nblocks;
-    p.nll = c->nblocks;
+    p.grid = (unsigned)c->map.nblocks;
+    p.nll = c->map.nblocks;
     if (c->wide) {
         // exchange images [2][2 NP][17] (+ the backward's masked-z images [2][NP][17]) and the per-block
         // reduction scratch (estep_mfma.hpp)
@@ -528,7 +484,7 @@ int plan_estep(hmmbw_ctx *c, bool fwd_only, const IterState *state, double *copi
             p.grid = (unsigned)c->wq_grid;
             a.wq = c->d_wq;
             a.wq_flag = c->d_wq + 2;
-            a.wq_units = (int)c->nblocks;
+            a.wq_units = (int)c->map.nblocks;
             a.wq_timeout_ticks = ms_to_ticks(c, c->wq_timeout_ms);
             if (!p.fn) return fail(HMMBW_E_UNSUPPORTED, "no wide work-queue kernel for N");
         }
@@ -545,22 +501,20 @@ int plan_estep(hmmbw_ctx *c, bool fwd_only, const IterState *state, double *copi
             const size_t tabs = c->lds_table_doubles();
             p.lds = sizeof(double) * (tabs + (size_t)wpb * c->G * NV + 8);
             // joined spread map: extra workgroup b's waves become waves 4.. of full workgroup b
-            if (!fwd_only && allow_join && joined_map(c) && ks.join_estep) {
+            if (!fwd_only && allow_join && joined(c->map, c->topo) && ks.join_estep) {
                 p.fn = ks.join_estep;
-                p.grid = (unsigned)c->nfull;
-                p.nll = c->nfull;
+                p.grid = (unsigned)c->map.nfull;
+                p.nll = c->map.nfull;
                 p.block = 2 * kBlock;
                 p.lds = sizeof(double) * (tabs + (size_t)(2 * wpb) * c->G * NV + 16);  // + [8 waves][2] LL pairs
-                if (split_tables_map(c) && ks.join_estep_split) {  // the class-split tables and their packs
+                // the class-split tables and their packs
+                if (split_tables_on(c->map, c->topo, c->d_sym2 != nullptr) && ks.join_estep_split) {
                     p.fn = ks.join_estep_split;
                     a.L.sym = c->d_sym2;
                     p.lds = sizeof(double) * (c->split_table_doubles() + (size_t)(2 * wpb) * c->G * NV + 16);
                 }
             }
-            // left-to-right: split extra waves on the joined map only (round 6, cfg3 29.63 -> 28.33 us,
-            // profiles/r6/split_lr_ab.txt); beside separate extra workgroups they cost more than they save
-            // (round 5: 34.0 -> 35.6 us)
-            if (lr && p.block != 2 * kBlock) a.split_extra = 0;
+            a.split_extra = split_extra_on(c->map, c->topo, p.block == 2 * kBlock) ? 1 : 0;
             if (HMMBW_ZFULL && !lr && !fwd_only) {  // dense: the forward stores every z_t (hmmbw_device.hpp)
                 if (int rc = ensure_zf(c)) return rc;
                 a.ckpt = c->d_zf;
@@ -668,6 +622,45 @@ static std::string device_error(const IterState &h) {
 
 }  // namespace hmmbw
 
+// the CSR input of hmmbw_set_observations; len: the sequences' lengths
+static int validate_obs(const hmmbw_ctx *c, const int64_t *offsets, const int32_t *symbols, int64_t R,
+                        std::vector<int> *len) {
+    if (!c || !offsets || (R > 0 && !symbols && offsets[R] > 0)) return fail(HMMBW_E_INVALID, "null argument");
+    if (R < 0) return fail(HMMBW_E_INVALID, "negative sequence count");
+    if (offsets[0] != 0) return fail(HMMBW_E_INVALID, "offsets[0] must be 0");
+    if (int rc = check_closed(c)) return rc;
+    len->resize((size_t)R);
+    for (int64_t r = 0; r < R; ++r) {
+        const int64_t T = offsets[r + 1] - offsets[r];
+        if (T < 0) return fail(HMMBW_E_INVALID, "offsets must be non-decreasing");
+        if (T == 0) return fail(HMMBW_E_EMPTY_SEQUENCE, "sequence " + std::to_string(r) + " is empty");
+        if (T > (1 << 28)) return fail(HMMBW_E_UNSUPPORTED, "sequence too long");
+        (*len)[(size_t)r] = (int)T;
+    }
+    for (int64_t i = 0; i < offsets[R]; ++i)
+        if (symbols[i] < 0 || symbols[i] >= c->K)
+            return fail(HMMBW_E_SYMBOL_RANGE, "symbol " + std::to_string(symbols[i]) + " at position " +
+                                                  std::to_string(i) + " is outside [0, M)");
+    return HMMBW_OK;
+}
+
+// A/B switches of the environment, read at every hmmbw_set_observations (before the map, which depends on them)
+static void read_switches(hmmbw_ctx *c) {
+    MapSwitches &sw = c->sw;
+    int v = 0;
+    env_int("HMMBW_PRIO", &c->prio);
+    if (env_int("HMMBW_SPLIT_EXTRA", &v)) sw.split_extra = v != 0;
+    if (env_int("HMMBW_JOIN", &v)) sw.join = v != 0;
+    if (env_int("HMMBW_JOIN_DENSE", &v)) sw.join_dense = v != 0;
+    sw.xact = env_int("HMMBW_XACT", &v) ? std::max(1, std::min(kWpb, v)) : 0;
+}
+
+template <class T>
+static int upload(T *dst, const std::vector<T> &v) {
+    if (!v.empty()) HIP_TRY(hipMemcpy(dst, v.data(), sizeof(T) * v.size(), hipMemcpyHostToDevice));
+    return HMMBW_OK;
+}
+
 extern "C" {
 
 int hmmbw_abi_version(void) { return HMMBW_ABI_VERSION; }
@@ -697,8 +690,9 @@ int hmmbw_ctx_create(int device, int n_states, int n_symbols, hmmbw_ctx **out) {
     c->NP = c->wide ? 16 * ((n_states + 15) / 16) : 0;
     c->G = c->wide ? c->NP : (n_states <= 2 ? 2 : n_states <= 4 ? 4 : n_states <= 8 ? 8 : 16);
     c->U = c->wide ? 16 : kWave / c->G;
-    if (const char *le = std::getenv("HMMBW_LDS_LAYOUT")) c->lds_layout = std::atoi(le) == 0 ? 0 : (std::atoi(le) == 1 ? 1 : -1);
-    if (const char *we = std::getenv("HMMBW_WIDE_WQ")) c->wq_mode = std::atoi(we) == 0 ? 0 : (std::atoi(we) == 1 ? 1 : -1);
+    int v = 0;
+    if (env_int("HMMBW_LDS_LAYOUT", &v)) c->sw.lds_layout = v == 0 ? 0 : (v == 1 ? 1 : -1);
+    if (env_int("HMMBW_WIDE_WQ", &v)) c->wq_mode = v == 0 ? 0 : (v == 1 ? 1 : -1);
     int rc = set_device(c);
     if (!rc) {
         int khz = 0;
@@ -805,217 +799,100 @@ int hmmbw_get_topology(const hmmbw_ctx *c, int *out) {
     return HMMBW_OK;
 }
 
+// validate, lay out, plan the map, allocate, upload, store
 int hmmbw_set_observations(hmmbw_ctx *c, const int64_t *offsets, const int32_t *symbols, int64_t R) {
-    if (!c || !offsets || (R > 0 && !symbols && offsets[R] > 0)) return fail(HMMBW_E_INVALID, "null argument");
-    if (R < 0) return fail(HMMBW_E_INVALID, "negative sequence count");
-    if (offsets[0] != 0) return fail(HMMBW_E_INVALID, "offsets[0] must be 0");
-    if (int rc = check_closed(c)) return rc;
-    std::vector<int> len((size_t)R);
-    for (int64_t r = 0; r < R; ++r) {
-        const int64_t T = offsets[r + 1] - offsets[r];
-        if (T < 0) return fail(HMMBW_E_INVALID, "offsets must be non-decreasing");
-        if (T == 0) return fail(HMMBW_E_EMPTY_SEQUENCE, "sequence " + std::to_string(r) + " is empty");
-        if (T > (1 << 28)) return fail(HMMBW_E_UNSUPPORTED, "sequence too long");
-        len[(size_t)r] = (int)T;
-    }
-    const int64_t total = offsets[R];
-    for (int64_t i = 0; i < total; ++i)
-        if (symbols[i] < 0 || symbols[i] >= c->K)
-            return fail(HMMBW_E_SYMBOL_RANGE, "symbol " + std::to_string(symbols[i]) + " at position " +
-                                                  std::to_string(i) + " is outside [0, M)");
+    std::vector<int> len;
+    if (int rc = validate_obs(c, offsets, symbols, R, &len)) return rc;
     if (int rc = set_device(c)) return rc;
     if (int rc = flush_mstep(c)) return rc;      // it reads this layout's log-likelihood pairs
     HIP_TRY(hipStreamSynchronize(c->stream));  // buffers may still be in use by enqueued work
-    // length-sorted (descending, stable) assignment of sequences to wave slots: the sequences that
-    // share a wave have near-equal lengths, so the lockstep time loop wastes little
-    std::vector<int64_t> perm((size_t)R);
-    std::iota(perm.begin(), perm.end(), 0);
-    std::stable_sort(perm.begin(), perm.end(), [&](int64_t x, int64_t y) { return len[x] > len[y]; });
-    const int U = c->U;
-    const long long nwaves = (R + U - 1) / U;
-    std::vector<long long> wsym((size_t)nwaves), wck((size_t)nwaves), wsp((size_t)nwaves);
-    std::vector<int> wT((size_t)nwaves), wfull((size_t)nwaves), slen((size_t)(nwaves * U), 0),
-        sseq((size_t)(nwaves * U), -1);
-    long long symtot = 0, cktot = 0, sptot = 0;
-    for (long long w = 0; w < nwaves; ++w) {
-        int Tw = 0, Tmin = 1 << 30;
-        for (int u = 0; u < U; ++u) {
-            const long long s = w * U + u;
-            if (s < R) {
-                slen[(size_t)s] = len[(size_t)perm[(size_t)s]];
-                sseq[(size_t)s] = (int)perm[(size_t)s];
-                Tw = std::max(Tw, slen[(size_t)s]);
-                Tmin = std::min(Tmin, slen[(size_t)s]);
-            }
-        }
-        const long long nch = (Tw + kChunk - 1) / kChunk;
-        wT[(size_t)w] = Tw;
-        wfull[(size_t)w] = (Tmin == Tw) ? 1 : 0;
-        wsym[(size_t)w] = symtot;
-        wck[(size_t)w] = cktot;
-        wsp[(size_t)w] = sptot;
-        symtot += nch * U * kChunk;
-        if (c->wide) {  // full alpha_hat [t][NP/16 waves][4][64 lanes] + exponents [t][16]
-            cktot += nch * kChunk * (long long)c->NP * 16;
-            sptot += nch * kChunk * 16;
-        } else {        // one checkpoint per chunk [c][64] + exponent packs [c][u]
-            cktot += nch * kWave;
-            sptot += nch * U;
-        }
-    }
+    const ObsLayout L = plan_layout(len, c->U, c->wide, c->NP);
+    const int64_t total = offsets[R];
     // packs hold LDS byte offsets of the emission record rows when the tables live in LDS (< 64 KiB,
     // so they fit uint16), symbol ids otherwise
-    const bool lds_off = c->lds_tables();
     const long long row_bytes = (long long)(c->G + kTabPad) * 16;  // 16-B table entries
-    std::vector<uint16_t> hsym((size_t)std::max(symtot, 1LL), 0);
-    for (long long w = 0; w < nwaves; ++w)
-        for (int u = 0; u < U; ++u) {
-            const long long s = w * U + u;
-            if (s >= R) continue;
-            const int64_t r = perm[(size_t)s];
-            const int T = len[(size_t)r];
-            for (int t = 0; t < T; ++t)
-                hsym[(size_t)(wsym[(size_t)w] + ((long long)(t / kChunk) * U + u) * kChunk + t % kChunk)] =
-                    (uint16_t)(lds_off ? symbols[offsets[r] + t] * row_bytes : symbols[offsets[r] + t]);
-        }
+    std::vector<uint16_t> hsym = fill_packs(L, offsets, symbols, c->lds_tables() ? row_bytes : 1);
     free_obs(c);
-    const int wpb = kBlock / kWave;
-    long long nblocks = c->wide ? nwaves : (nwaves + wpb - 1) / wpb;  // wide: one tile per block
-    // Small kernels, more waves than SIMDs: one full 4-wave workgroup per CU, then the remaining waves
-    // in workgroups of xact = 2 active waves (one per CU while they fit), so the SIMDs that must run a
-    // second wave are spread over twice as many CUs, which then share their LDS and memory pipes among
-    // 6 waves instead of 8.  cfg3 (1,250 waves): 38.2 -> 36.5 us per iteration; xact = 1 (a prologue
-    // and histogram flush per extra wave) and 3 measured no better.  HMMBW_XACT
-    // overrides it (diagnostics: 1..4, 4 = every workgroup full).
-    // A/B switches (read before the map, which depends on the split)
-    if (const char *pe = std::getenv("HMMBW_PRIO")) c->prio = std::atoi(pe);
-    if (const char *se = std::getenv("HMMBW_SPLIT_EXTRA")) c->split_extra = std::atoi(se) != 0;
-    if (const char *je = std::getenv("HMMBW_JOIN")) c->join = std::atoi(je) != 0;
-    if (const char *jd = std::getenv("HMMBW_JOIN_DENSE")) c->join_dense = std::atoi(jd) != 0;
-    long long nfull = nblocks;
-    int xact = wpb;
-    if (!c->wide && !c->det) {
-        int ncu = 0;
-        (void)hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, c->device);
-        if (ncu > 0 && nwaves > (long long)ncu * wpb) {
-            const long long extra = nwaves - (long long)ncu * wpb;
-            const char *xe = std::getenv("HMMBW_XACT");
-            int xa = extra <= 2LL * ncu ? 2 : wpb;
-            // dense (as requested before the observations) with the split extra waves: one group per extra
-            // workgroup while they fit one per CU (cfg3 dense 63.5 -> 62.2 us, profiles/r5/spread_knobs.txt)
-            if (c->topo_req == HMMBW_TOPOLOGY_DENSE && c->split_extra && extra <= ncu) xa = 1;
-            if (xe) xa = std::max(1, std::min(wpb, std::atoi(xe)));
-            // left-to-right on the joined map: past 2 extra groups per CU they still join the full workgroups,
-            // up to 4 per CU (cfg4 shard, 12,500 sequences: 135 workgroups of 8 waves instead of 2 x 135 of 4)
-            const bool join4 = !xe && xa == wpb && c->join && c->topo_req != HMMBW_TOPOLOGY_DENSE;
-            if ((xa < wpb || join4) && (extra + xa - 1) / xa <= ncu) {
-                nfull = ncu;
-                xact = xa;
-                nblocks = nfull + (extra + xa - 1) / xa;
-            }
-        }
-    }
-    int rc = dalloc(&c->d_sym, (size_t)std::max(symtot, 1LL));
-    // (symtot / U: the waves' steps, each wave's rounded up to whole chunks)
-    const bool sym2 = c->split_tables() && split_tables_policy(c, nblocks, nfull, symtot / U, nwaves);
-    if (!rc && sym2) rc = dalloc(&c->d_sym2, (size_t)std::max(symtot, 1LL));
-    if (!rc) rc = dalloc(&c->d_wsym, (size_t)nwaves);
-    if (!rc) rc = dalloc(&c->d_wckoff, (size_t)nwaves);
-    if (!rc) rc = dalloc(&c->d_wspoff, (size_t)nwaves);
-    if (!rc) rc = dalloc(&c->d_wT, (size_t)nwaves);
-    if (!rc) rc = dalloc(&c->d_wfull, (size_t)nwaves);
-    if (!rc) rc = dalloc(&c->d_slen, (size_t)(nwaves * U));
-    if (!rc) rc = dalloc(&c->d_sseq, (size_t)(nwaves * U));
-    if (!rc) rc = dalloc(&c->d_ck, (size_t)std::max(cktot, 1LL));
-    c->cktot = cktot;
-    if (!rc) {
-        if (c->wide) rc = dalloc(&c->d_ebuf, (size_t)std::max(sptot, 1LL));
-        else rc = dalloc(&c->d_sp, (size_t)std::max(sptot, 1LL));
-    }
+
+    read_switches(c);
+    MapInputs in;
+    in.nwaves = L.nwaves;
+    in.steps = L.symtot / L.U;
+    (void)hipDeviceGetAttribute(&in.ncu, hipDeviceAttributeMultiprocessorCount, c->device);
+    in.wide = c->wide;
+    in.det = c->det;
+    in.lds_tables = c->lds_tables();
+    in.split_tables = c->split_tables();
+    in.topo_req = c->topo_req;
+    in.sw = c->sw;
+    const LaunchMap m = plan_map(in);
+
+    // symbol -> gamma rows index of k_bnum_gather (wide path, deterministic mode)
     std::vector<long long> bptr;
     std::vector<unsigned> brows;
     if (c->wide) {
         // position -> its row in symbol order (positions of one symbol in tile-row order): the E-step writes
         // the gamma row of tile row wck / NP + t * 16 + u there (brows, indexed by tile row), so symbol k's
         // rows are [bptr[k], bptr[k+1]) and k_bnum_gather streams them
-        if (cktot / c->NP >= (1LL << 32)) return fail(HMMBW_E_UNSUPPORTED, "too many positions for the wide path");
-        bptr.assign((size_t)c->K + 1, 0);
-        for (int64_t i = 0; i < total; ++i) ++bptr[(size_t)symbols[i] + 1];
-        for (int k = 0; k < c->K; ++k) bptr[(size_t)k + 1] += bptr[(size_t)k];
-        std::vector<long long> fill(bptr.begin(), bptr.end() - 1);
+        if (L.cktot / c->NP >= (1LL << 32)) return fail(HMMBW_E_UNSUPPORTED, "too many positions for the wide path");
         // rows of padding slots (a tile's slots past the last sequence: full-tile code paths store their
         // exact-zero gamma rows unmasked) all go to one scratch row past the real ones
-        brows.assign((size_t)std::max(cktot / c->NP, 1LL), (unsigned)total);
-        for (long long w = 0; w < nwaves; ++w)
-            for (int u = 0; u < U; ++u) {
-                const long long sl = w * U + u;
-                if (sl >= R) continue;
-                const int64_t r = perm[(size_t)sl];
-                for (int t = 0; t < len[(size_t)r]; ++t)
-                    brows[(size_t)(wck[(size_t)w] / c->NP + (long long)t * U + u)] =
-                        (unsigned)fill[(size_t)symbols[offsets[r] + t]]++;
-            }
-        if (!rc) rc = dalloc(&c->d_gam, (size_t)(total + 1) * c->NP);
-        if (!rc) rc = dalloc(&c->d_bptr, bptr.size());
-        if (!rc) rc = dalloc(&c->d_brows, brows.size());
-        if (!rc && c->det) rc = dalloc(&c->d_part, (size_t)std::max(nblocks, 1LL) * (size_t)c->off_bnum());
+        brows.assign((size_t)std::max(L.cktot / c->NP, 1LL), (unsigned)total);
+        build_gather_index(L, offsets, symbols, c->K, true, [&](long long w, int u, int t) {
+            return L.ckoff[(size_t)w] / c->NP + (long long)t * L.U + u;
+        }, bptr, brows);
     } else if (c->det) {  // deterministic mode: symbol -> pack positions (gamma row = pack index), stable
-        if (symtot >= (1LL << 32)) return fail(HMMBW_E_UNSUPPORTED, "too many positions for the deterministic mode");
-        bptr.assign((size_t)c->K + 1, 0);
-        for (int64_t i = 0; i < total; ++i) ++bptr[(size_t)symbols[i] + 1];
-        for (int k = 0; k < c->K; ++k) bptr[(size_t)k + 1] += bptr[(size_t)k];
-        std::vector<long long> fill(bptr.begin(), bptr.end() - 1);
+        if (L.symtot >= (1LL << 32)) return fail(HMMBW_E_UNSUPPORTED, "too many positions for the deterministic mode");
         brows.resize((size_t)std::max<int64_t>(total, 1));
-        for (long long w = 0; w < nwaves; ++w)
-            for (int u = 0; u < U; ++u) {
-                const long long sl = w * U + u;
-                if (sl >= R) continue;
-                const int64_t r = perm[(size_t)sl];
-                for (int t = 0; t < len[(size_t)r]; ++t)
-                    brows[(size_t)fill[(size_t)symbols[offsets[r] + t]]++] =
-                        (unsigned)(wsym[(size_t)w] + ((long long)(t / kChunk) * U + u) * kChunk + t % kChunk);
-            }
-        if (!rc) rc = dalloc(&c->d_gam, (size_t)std::max(symtot, 1LL) * c->G);
+        build_gather_index(L, offsets, symbols, c->K, false, [&](long long w, int u, int t) {
+            return pack_pos(L.symoff[(size_t)w], L.U, u, t);
+        }, bptr, brows);
+    }
+
+    const size_t nw = (size_t)L.nwaves, nb1 = (size_t)std::max(m.nblocks, 1LL);
+    int rc = dalloc(&c->d_sym, hsym.size());
+    if (!rc && m.sym2) rc = dalloc(&c->d_sym2, hsym.size());
+    if (!rc) rc = dalloc(&c->d_wsym, nw);
+    if (!rc) rc = dalloc(&c->d_wckoff, nw);
+    if (!rc) rc = dalloc(&c->d_wspoff, nw);
+    if (!rc) rc = dalloc(&c->d_wT, nw);
+    if (!rc) rc = dalloc(&c->d_wfull, nw);
+    if (!rc) rc = dalloc(&c->d_slen, L.slot_len.size());
+    if (!rc) rc = dalloc(&c->d_sseq, L.slot_seq.size());
+    if (!rc) rc = dalloc(&c->d_ck, (size_t)std::max(L.cktot, 1LL));
+    c->cktot = L.cktot;
+    const size_t nsp = (size_t)std::max(L.sptot, 1LL);
+    if (!rc) rc = c->wide ? dalloc(&c->d_ebuf, nsp) : dalloc(&c->d_sp, nsp);
+    if (c->wide || c->det) {  // gamma rows: per position (wide), per pack entry (deterministic mode)
+        if (!rc) rc = dalloc(&c->d_gam, c->wide ? (size_t)(total + 1) * c->NP : hsym.size() * c->G);
         if (!rc) rc = dalloc(&c->d_bptr, bptr.size());
         if (!rc) rc = dalloc(&c->d_brows, brows.size());
-        if (!rc) rc = dalloc(&c->d_part, (size_t)std::max(nblocks, 1LL) * (size_t)c->off_bnum());
+        if (!rc && c->det) rc = dalloc(&c->d_part, nb1 * (size_t)c->off_bnum());
     }
     if (!rc) rc = dalloc(&c->d_logp, (size_t)std::max<int64_t>(R, 1));
-    if (!rc) rc = dalloc(&c->d_llpart, 4 * (size_t)std::max(nblocks, 1LL));
+    if (!rc) rc = dalloc(&c->d_llpart, 4 * nb1);
+
+    if (!rc) rc = upload(c->d_sym, hsym);
+    if (!rc && m.sym2) {
+        to_split_packs(hsym, row_bytes, c->G);
+        rc = upload(c->d_sym2, hsym);
+    }
+    if (!rc && (c->wide || c->det)) rc = upload(c->d_bptr, bptr);
+    if (!rc && (c->wide || c->det)) rc = upload(c->d_brows, brows);
+    if (!rc) rc = upload(c->d_wsym, L.symoff);
+    if (!rc) rc = upload(c->d_wckoff, L.ckoff);
+    if (!rc) rc = upload(c->d_wspoff, L.spoff);
+    if (!rc) rc = upload(c->d_wT, L.wave_T);
+    if (!rc) rc = upload(c->d_wfull, L.wave_full);
+    if (!rc) rc = upload(c->d_slen, L.slot_len);
+    if (!rc) rc = upload(c->d_sseq, L.slot_seq);
+    if (!rc) rc = upload(c->d_logp, std::vector<double>((size_t)std::max<int64_t>(R, 1), -INFINITY));
+    if (!rc) rc = upload(c->d_llpart, std::vector<double>(4 * nb1, 0.0));
     if (rc) return rc;
-    HIP_TRY(hipMemcpy(c->d_sym, hsym.data(), sizeof(uint16_t) * hsym.size(), hipMemcpyHostToDevice));
-    if (sym2) {  // the class-split rows are twice as long: o * row_bytes -> o * lay2_row_bytes (<= 65,280)
-        static_assert(lay2_row_bytes(8) == 2 * 8 * 16, "class-split row stride");
-        for (uint16_t &e : hsym) e = (uint16_t)(e / row_bytes * lay2_row_bytes(c->G));
-        HIP_TRY(hipMemcpy(c->d_sym2, hsym.data(), sizeof(uint16_t) * hsym.size(), hipMemcpyHostToDevice));
-    }
-    if (c->wide || c->det) {
-        HIP_TRY(hipMemcpy(c->d_bptr, bptr.data(), sizeof(long long) * bptr.size(), hipMemcpyHostToDevice));
-        HIP_TRY(hipMemcpy(c->d_brows, brows.data(), sizeof(unsigned) * brows.size(), hipMemcpyHostToDevice));
-    }
-    if (nwaves > 0) {
-        HIP_TRY(hipMemcpy(c->d_wsym, wsym.data(), sizeof(long long) * nwaves, hipMemcpyHostToDevice));
-        HIP_TRY(hipMemcpy(c->d_wckoff, wck.data(), sizeof(long long) * nwaves, hipMemcpyHostToDevice));
-        HIP_TRY(hipMemcpy(c->d_wspoff, wsp.data(), sizeof(long long) * nwaves, hipMemcpyHostToDevice));
-        HIP_TRY(hipMemcpy(c->d_wT, wT.data(), sizeof(int) * nwaves, hipMemcpyHostToDevice));
-        HIP_TRY(hipMemcpy(c->d_wfull, wfull.data(), sizeof(int) * nwaves, hipMemcpyHostToDevice));
-        HIP_TRY(hipMemcpy(c->d_slen, slen.data(), sizeof(int) * nwaves * U, hipMemcpyHostToDevice));
-        HIP_TRY(hipMemcpy(c->d_sseq, sseq.data(), sizeof(int) * nwaves * U, hipMemcpyHostToDevice));
-    }
-    std::vector<double> ninf((size_t)std::max<int64_t>(R, 1), -INFINITY);
-    HIP_TRY(hipMemcpy(c->d_logp, ninf.data(), sizeof(double) * ninf.size(), hipMemcpyHostToDevice));
-    std::vector<double> zpairs(4 * (size_t)std::max(nblocks, 1LL), 0.0);
-    HIP_TRY(hipMemcpy(c->d_llpart, zpairs.data(), sizeof(double) * zpairs.size(), hipMemcpyHostToDevice));
+
     c->R = R;
-    c->nwaves = nwaves;
-    c->nblocks = nblocks;
-    c->nfull = nfull;
-    {
-        int ncu = 0;
-        (void)hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, c->device);
-        c->fits_cus = ncu > 0 && nblocks <= ncu;
-    }
-    c->xact = xact;
+    c->nwaves = L.nwaves;
+    c->map = m;
     c->has_obs = true;
     if (int rc2 = ensure_wq(c)) return rc2;
     return ensure_zf(c);
@@ -1047,7 +924,7 @@ int hmmbw_set_option(hmmbw_ctx *c, int key, int64_t value) {
         if (value < -1 || value > 1)
             return fail(HMMBW_E_INVALID, "HMMBW_OPT_LDS_LAYOUT: -1 (auto), 0 (row tables) or 1 (class-split)");
         if (c->has_obs) return fail(HMMBW_E_STATE, "set the LDS table layout before hmmbw_set_observations");
-        c->lds_layout = (int)value;
+        c->sw.lds_layout = (int)value;
         return HMMBW_OK;
     }
     if (key == HMMBW_OPT_MERGE_MSTEP) {
@@ -1118,16 +995,20 @@ int hmmbw_get_option(const hmmbw_ctx *c, int key, int64_t *value) {
         case HMMBW_OPT_LIVE_STATUS: *value = c->h_live ? 1 : 0; return HMMBW_OK;
         case HMMBW_OPT_WQ_TIMEOUT_MS: *value = c->wq_timeout_ms; return HMMBW_OK;
         case HMMBW_OPT_WIDE_WQ: *value = c->wq_mode; return HMMBW_OK;
-        case HMMBW_OPT_LDS_LAYOUT: *value = c->lds_layout; return HMMBW_OK;
-        case HMMBW_INFO_LDS_LAYOUT: *value = c->has_obs && split_tables_map(c) ? 1 : 0; return HMMBW_OK;
+        case HMMBW_OPT_LDS_LAYOUT: *value = c->sw.lds_layout; return HMMBW_OK;
+        case HMMBW_INFO_LDS_LAYOUT:
+            *value = c->has_obs && split_tables_on(c->map, c->topo, c->d_sym2 != nullptr) ? 1 : 0;
+            return HMMBW_OK;
         case HMMBW_INFO_WIDE_WQ_ACTIVE: *value = c->d_wq ? 1 : 0; return HMMBW_OK;
-        case HMMBW_INFO_WAVES: *value = c->wide ? c->nblocks * (c->NP / 16) : c->nwaves; return HMMBW_OK;
-        case HMMBW_INFO_WORKGROUPS: *value = c->d_wq ? c->wq_grid : c->nblocks; return HMMBW_OK;
+        case HMMBW_INFO_WAVES: *value = c->wide ? c->map.nblocks * (c->NP / 16) : c->nwaves; return HMMBW_OK;
+        case HMMBW_INFO_WORKGROUPS: *value = c->d_wq ? c->wq_grid : c->map.nblocks; return HMMBW_OK;
         case HMMBW_INFO_WAVES_PER_WORKGROUP: *value = c->wide ? c->NP / 16 : kBlock / kWave; return HMMBW_OK;
-        case HMMBW_INFO_FULL_WORKGROUPS: *value = c->wide ? c->nblocks : std::min(c->nfull, c->nblocks); return HMMBW_OK;
-        case HMMBW_INFO_EXTRA_WAVES: *value = c->wide ? 0 : c->xact; return HMMBW_OK;
-        case HMMBW_INFO_JOINED: *value = c->has_obs && joined_map(c) ? 1 : 0; return HMMBW_OK;
-        case HMMBW_INFO_SPLIT_EXTRA: *value = c->has_obs && split_extra_map(c) ? 1 : 0; return HMMBW_OK;
+        case HMMBW_INFO_FULL_WORKGROUPS: *value = c->wide ? c->map.nblocks : std::min(c->map.nfull, c->map.nblocks); return HMMBW_OK;
+        case HMMBW_INFO_EXTRA_WAVES: *value = c->wide ? 0 : c->map.xact; return HMMBW_OK;
+        case HMMBW_INFO_JOINED: *value = c->has_obs && joined(c->map, c->topo) ? 1 : 0; return HMMBW_OK;
+        case HMMBW_INFO_SPLIT_EXTRA:
+            *value = c->has_obs && split_extra_on(c->map, c->topo, joined(c->map, c->topo)) ? 1 : 0;
+            return HMMBW_OK;
         case HMMBW_INFO_PEER_CHUNKS:
         case HMMBW_INFO_PEER_SUM_PTR:
         case HMMBW_INFO_PEER_REGIONS_VALIDATED:
@@ -1176,7 +1057,7 @@ int hmmbw_reset_training(hmmbw_ctx *c, double epsilon, int64_t max_iterations) {
     if (c->d_xbuf) HIP_TRY(hipMemsetAsync(c->d_xbuf, 0, sizeof(double) * 3 * (size_t)c->xlen, c->stream));
     // the work queue's counters and flags: a run stopped by a work-queue timeout leaves them armed (the
     // workgroups that start after the stop return at once and never reach the re-arm)
-    if (c->d_wq) HIP_TRY(hipMemsetAsync(c->d_wq, 0, sizeof(unsigned) * ((size_t)c->nblocks + 2), c->stream));
+    if (c->d_wq) HIP_TRY(hipMemsetAsync(c->d_wq, 0, sizeof(unsigned) * ((size_t)c->map.nblocks + 2), c->stream));
     // the fused multi-rank completion counter: workgroups that start after a device-side stop return
     // before counting their log-likelihood pair, so a stopped launch leaves it part-way; the next run's
     // last-workgroup fold must start from zero
@@ -1248,7 +1129,7 @@ static int mr_begin(hmmbw_ctx *c, long long n_seq_global, double **buf, long lon
         double *X = c->d_xbuf + (e % 3) * c->xlen, *Xn = c->d_xbuf + ((e + 1) % 3) * c->xlen;
         const long long ll_off = (long long)nc * c->copy_len();
         // accumulate into X (the merged M-step reads the previous, all-reduced X), clear the next
-        if (c->nblocks > 0) {
+        if (c->map.nblocks > 0) {
             if (int rc = launch_estep(c, false, c->state(), X, c->llpart(e), Xn, c->xlen, true,
                                       X + ll_off + 2LL * c->rank, nc))
                 return rc;

@@ -16,6 +16,7 @@
 #include <vector>
 
 #include "lds_layout.hpp"
+#include "obs_plan.hpp"
 
 #include "../../include/hmmbw.h"
 
@@ -83,14 +84,12 @@ static __device__ unsigned long long g_chunk[4096][2][64];
 #define HMMBW_ZF_NT 0
 #endif
 
-constexpr int kWave = 64;
-constexpr int kChunk = 8;  // time steps per packed symbol load (8 x uint16 = 16 B)
+// kWave, kChunk, kBlock: obs_plan.hpp
 #ifndef HMMBW_KSCALE
 #define HMMBW_KSCALE 8
 #endif
 constexpr int kScale = HMMBW_KSCALE;  // lagged mode: the forward rescales every kScale steps
 constexpr int kHist = 4096;
-constexpr int kBlock = 256;  // threads per E-step workgroup (4 waves)
 
 struct IterState {
     double prev_L;
@@ -601,6 +600,7 @@ __device__ __forceinline__ void estep_small_body(const EArgs &a, const long long
     bool merged = false;
     if constexpr (LDSTAB && !FWD_ONLY) merged = a.merged != 0;
     const int wpb = JOIN ? kBlock / kWave : blockDim.x >> 6;  // waves of a full (sequence-group) workgroup
+    // (wave_role in obs_plan.hpp states the block below for the host and its CPU test: change the two together)
     const bool xblk = JOIN ? wv >= wpb : bid >= a.nfull;     // this wave runs an extra group
     const int wx = JOIN ? wv - wpb : wv;                      // index among the extra group's waves
     // split extra waves: with 2 xact <= 4 extra waves, extra wave wx in [xact, 2 xact) is the B partner of extra

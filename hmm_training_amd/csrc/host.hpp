@@ -2,6 +2,8 @@
 // allocator's interface, the timing event pool, the launch plan, the context and the few helpers that
 // cross units.  Owners: alloc.hip (block cache, ledger), peer.hip (peer all-reduce), comm.hip (RCCL),
 // group.hip (grouped launches), hmmbw.hip (everything else, and the definitions of the helpers below).
+// The observation layout and the launch map hmmbw.hip plans are obs_plan.hpp's: pure, shared with the
+// kernels, tested without a GPU (tests/test_obs_plan.py).
 #pragma once
 
 #include <algorithm>
@@ -127,17 +129,11 @@ struct hmmbw_ctx {
     } pend;
     // observations
     long long R = 0, nwaves = 0;
-    long long nblocks = 0;
-    long long nfull = 0;          // small kernels: workgroups with 4 active waves (then xact-wave ones)
-    int xact = 4;
+    MapSwitches sw;               // the map's A/B switches and HMMBW_OPT_LDS_LAYOUT (obs_plan.hpp)
+    LaunchMap map;                // the wave -> workgroup launch map of the observations (obs_plan.hpp, plan_map;
+                                  // stored by set_observations with everything else)
     int prio = -1;                // wave priority of the small kernels (EArgs::prio): -1 auto (left-to-right 2,
                                   // dense 0: profiles/r5/spread_knobs.txt); HMMBW_PRIO overrides it
-    int split_extra = 1;          // EArgs::split_extra (HMMBW_SPLIT_EXTRA=0 turns it off)
-    int join = 1;                 // left-to-right E-step on the joined spread map (k_estep_join; HMMBW_JOIN=0 off)
-    int join_dense = 1;           // the dense E-step on it too (HMMBW_JOIN_DENSE=0 off)
-    int lds_layout = -1;          // HMMBW_OPT_LDS_LAYOUT: the joined map on the class-split LDS tables (G = 8):
-                                  // -1 where they pay (hmmbw.hip, split_tables_map), 0 never, 1 wherever they can run
-    bool fits_cus = false;        // the launch map's workgroups fit one per CU (set_observations)
     long long last_nll = 0;       // per-workgroup log-likelihood pairs written by the last E-step launch
     uint16_t *d_sym = nullptr;
     uint16_t *d_sym2 = nullptr;   // the packs of the class-split tables (row offsets o 2 G 16), or nullptr: the
@@ -219,7 +215,6 @@ struct hmmbw_ctx {
     long long off_ll() const { return off_bnum() + (long long)K * N; }
     long long stats_len() const { return off_ll() + 2LL * world; }
     long long copy_len() const { return off_ll(); }
-    // emission table + B-numerator histogram in LDS ([K][G+1] fp64 each) when they fit 48 KiB
     // emission P/H tables in LDS (two [K][G + kTabPad] tables of 16-B entries kHistOff bytes apart, see
     // hmmbw_device.hpp) when the first fits below kHistOff (the row offsets then fit the uint16 packs)
     bool lds_tables() const { return !wide && lds_tables_fit(K, G + kTabPad); }
@@ -228,7 +223,7 @@ struct hmmbw_ctx {
     // the class-split tables (lds_layout.hpp, lay2_p_off) can serve this context's joined launches: G = 8,
     // the rows of one class within 64 KiB (uint16 packs); both classes then fit the CU's 160 KiB with the scratch
     bool split_tables() const {
-        return lds_layout != 0 && !wide && !det && kTabPad == 0 && G == 8 && lds_tables() && lay2_tables_fit(K, G);
+        return sw.lds_layout != 0 && !wide && !det && kTabPad == 0 && G == 8 && lds_tables() && lay2_tables_fit(K, G);
     }
     size_t split_table_doubles() const { return lay2_table_bytes(K, G) / sizeof(double); }
     bool can_merge() const { return merge_mstep && lds_tables() && copy_len() <= kMergedMaxStats && nwaves > 0; }
@@ -244,7 +239,7 @@ struct hmmbw_ctx {
     bool peer_mode() const { return ar_kind == HMMBW_ALLREDUCE_PEER && peer.on; }
     IterState *state() const { return d_state + scur; }
     double *copies(long long e) const { return d_copies + (e % 3) * (long long)ncopies * copy_len(); }
-    double *llpart(long long e) const { return d_llpart + (e % 2) * 2 * std::max(nblocks, 1LL); }
+    double *llpart(long long e) const { return d_llpart + (e % 2) * 2 * std::max(map.nblocks, 1LL); }
 };
 
 namespace hmmbw {
