@@ -34,7 +34,7 @@
 // Host units (host.hpp): this one holds the context's life cycle, observations, options and parameters,
 // the launch planner, hmmbw_estep / _mstep / _iterate*, status, scoring and timing; alloc.hip the block
 // cache and the allocation ledger, peer.hip the peer all-reduce (kernels included), comm.hip the RCCL
-// communicator, group.hip the grouped launches.
+// communicator, group.hip the grouped launches, viterbi.hip the Viterbi decoder.
 #include <atomic>
 #include <map>
 #include <mutex>
@@ -248,6 +248,7 @@ static void free_obs(hmmbw_ctx *c) {
     dfree(c->d_wT); dfree(c->d_wfull); dfree(c->d_slen); dfree(c->d_sseq);
     dfree(c->d_ck); dfree(c->d_sp); dfree(c->d_ebuf); dfree(c->d_logp); dfree(c->d_llpart); dfree(c->d_zf);
     dfree(c->d_gam); dfree(c->d_bptr); dfree(c->d_brows); dfree(c->d_part); dfree(c->d_wq);
+    viterbi_free(c);
     c->wq_grid = 0;
     c->has_obs = false;
 }
@@ -892,6 +893,8 @@ int hmmbw_set_observations(hmmbw_ctx *c, const int64_t *offsets, const int32_t *
 
     c->R = R;
     c->nwaves = L.nwaves;
+    c->h_slen = L.slot_len;
+    c->h_sseq = L.slot_seq;
     c->map = m;
     c->has_obs = true;
     if (int rc2 = ensure_wq(c)) return rc2;

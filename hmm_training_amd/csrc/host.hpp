@@ -1,7 +1,8 @@
 // host.hpp — what the host-side units share (internal; declarations only): the error channel, the
 // allocator's interface, the timing event pool, the launch plan, the context and the few helpers that
 // cross units.  Owners: alloc.hip (block cache, ledger), peer.hip (peer all-reduce), comm.hip (RCCL),
-// group.hip (grouped launches), hmmbw.hip (everything else, and the definitions of the helpers below).
+// group.hip (grouped launches), viterbi.hip (hmmbw_viterbi and its kernels), hmmbw.hip (everything else, and the
+// definitions of the helpers below).
 // The observation layout and the launch map hmmbw.hip plans are obs_plan.hpp's: pure, shared with the
 // kernels, tested without a GPU (tests/test_obs_plan.py).
 #pragma once
@@ -15,6 +16,7 @@
 
 #include "hmmbw_device.hpp"
 #include "hmmbw_kernels.hpp"
+#include "viterbi_plan.hpp"
 
 namespace hmmbw {
 
@@ -153,6 +155,18 @@ struct hmmbw_ctx {
     long long wq_timeout_ms = 10000;  // HMMBW_OPT_WQ_TIMEOUT_MS: bound of a backward unit's wait
     uint4 *d_sp = nullptr;
     int *d_ebuf = nullptr;
+    // hmmbw_viterbi (viterbi.hip): the host's copy of the layout's slot arrays (set_observations) and the
+    // decoder's buffers, allocated on first use and freed with the observations
+    std::vector<int> h_slen, h_sseq;
+    struct Viterbi {
+        bool planned = false;
+        ViterbiPlan plan;                 // slot_out / psi_off are moved to the device, the figures stay
+        double *d_tab = nullptr;          // [GV] log pi | [GV][GV] log A (lane j's column contiguous) | [K][GV] log B^T
+        long long *d_slot_out = nullptr, *d_psi_off = nullptr;
+        double *d_logp = nullptr;
+        int32_t *d_path = nullptr;        // with paths only: caller CSR order
+        unsigned char *d_psi = nullptr;   // with paths only: back-pointers, [t][64 lanes] bytes per decoding wave
+    } vit;
     // native RCCL communicator (hmmbw_comm_init): the multi-rank hmmbw_iterate all-reduces d_ext
     ncclComm_t comm = nullptr;
     double *d_ext = nullptr;      // non-fused multi-rank paths: the packed statistics to all-reduce
@@ -260,6 +274,9 @@ int plan_estep(hmmbw_ctx *c, bool fwd_only, const IterState *state, double *copi
 int launch_estep(hmmbw_ctx *c, bool fwd_only, const IterState *state, double *copies = nullptr,
                  double *llpart = nullptr, double *zero = nullptr, long long zero_len = 0, bool merge = false,
                  double *rank_ll = nullptr, int ncopies = 0);
+
+// viterbi.hip
+void viterbi_free(hmmbw_ctx *c);  // the decoder's buffers; callers synchronise the context first
 
 // peer.hip
 std::string peer_off_msg(const hmmbw_ctx *c);

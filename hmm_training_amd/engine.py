@@ -169,6 +169,7 @@ class BaumWelchEngine:
         check(self._lib.hmmbw_set_observations(self._ctx, offsets.ctypes.data, symbols.ctypes.data, R))
         self.n_seq = R
         self.n_symbols_total = int(offsets[-1]) if R > 0 else 0
+        self._offsets = offsets.copy()  # viterbi() splits the path by them
         self.n_seq_global = R if n_seq_global is None else int(n_seq_global)
         if self._want_native and self._native_R != self.n_seq_global:
             want_rccl = self.allreduce_req in ("rccl", "both")
@@ -545,6 +546,18 @@ class BaumWelchEngine:
         out = np.zeros(max(self.n_seq, 1))
         check(self._lib.hmmbw_score(self._ctx, out.ctypes.data))
         return out[: self.n_seq]
+
+    def viterbi(self, paths: bool = True) -> Tuple[Optional[List[np.ndarray]], np.ndarray]:
+        """Viterbi decoding of every loaded sequence under the current parameters (hmmbw_viterbi):
+        (paths, logp).  paths: one int32 state array per sequence (all -1 where logp is -inf), or None with
+        paths=False (scores only: no back-pointers are stored); logp: the best path's log-probability."""
+        logp = np.zeros(max(self.n_seq, 1))
+        total = getattr(self, "n_symbols_total", 0)
+        flat = np.zeros(max(total, 1), dtype=np.int32) if paths else None
+        check(self._lib.hmmbw_viterbi(self._ctx, logp.ctypes.data, flat.ctypes.data if paths else None, total))
+        if not paths:
+            return None, logp[: self.n_seq]
+        return np.split(flat[:total], self._offsets[1:-1]) if self.n_seq else [], logp[: self.n_seq]
 
     def timing(self, enable: int = -1) -> Tuple[float, int]:
         """(accumulated E-step ms, timed launches) of hmmbw_timing; enable >= 0 also resets and sets the

@@ -55,6 +55,19 @@ def score_matrix(observations: Sequence[np.ndarray], models: Sequence[HMMTrained
     return out
 
 
+def viterbi_decode(observations: Sequence[np.ndarray], hmm: HMMTrained, device=None) -> Tuple[List[np.ndarray], np.ndarray]:
+    """(paths, logp): the most likely state sequence of every recording under one model and its
+    log-probability, all sequences in one launch (BaumWelchEngine.viterbi).  A sequence no path explains has
+    logp -inf and a path of -1."""
+    if len(observations) == 0:
+        return [], np.zeros(0)
+    N, M = int(hmm.states), int(np.asarray(hmm.B).shape[1])
+    with BaumWelchEngine(N, M, device=device) as eng:
+        eng.set_observations(observations)
+        eng.set_params(np.asarray(hmm.Pi), np.asarray(hmm.A), np.asarray(hmm.B))
+        return eng.viterbi()
+
+
 def calculate_log_likelihood(recording_observations: np.ndarray, hmm: HMMTrained) -> float:
     """log P(O | lambda) of one sequence under one linear-domain model (hmm_testing.py:49-104)."""
     return float(score_matrix([np.asarray(recording_observations)], [hmm])[0, 0])

@@ -37,7 +37,9 @@ extern "C" {
                               4: live status mirror (HMMBW_OPT_LIVE_STATUS, hmmbw_status_live_wait);
                               5: hmmbw_get_option, HMMBW_OPT_WQ_TIMEOUT_MS, HMMBW_OPT_WIDE_WQ
                                  (HMMBW_OPT_LDS_LAYOUT / HMMBW_INFO_LDS_LAYOUT are new keys of the same calls:
-                                 an older library answers them HMMBW_E_INVALID, no entry point changed) */
+                                 an older library answers them HMMBW_E_INVALID, no entry point changed;
+                                 hmmbw_viterbi is a new entry point of version 5: an older library lacks the
+                                 symbol) */
 
 #define HMMBW_OK 0
 #define HMMBW_E_INVALID (-1)        /* bad argument (shape, range, null pointer)             */
@@ -233,6 +235,20 @@ int hmmbw_get_loglik(hmmbw_ctx *ctx, double *out);
 /* SYNC. Forward-only scoring of the loaded sequences under the current parameters:
  * hmm_testing.py:49-104 calculate_log_likelihood for every sequence, one launch. */
 int hmmbw_score(hmmbw_ctx *ctx, double *out);
+
+/* SYNC. Viterbi decoding of the loaded sequences under the current parameters, log domain, fp64:
+ *   delta_0(j) = log pi_j + log b_j(o_0)
+ *   delta_t(j) = max_i (delta_{t-1}(i) + log a_ij) + log b_j(o_t)
+ *   psi_t(j)   = the SMALLEST i attaining the max (strict '>' scan from i = 0)
+ *   end state  = the smallest j attaining max_j delta_{T-1}(j)
+ * log 0 = -inf; a -inf candidate never wins against a finite one.
+ * logp_out[r] (R doubles, caller order): the best path's log-probability, -inf if no path has positive
+ * probability.  path_out (may be NULL: scores only, no back-pointers are stored): int32, caller CSR order,
+ * path_out[offsets[r] + t] = state at step t; every entry of a sequence whose logp is -inf is -1.
+ * path_len must equal the total number of loaded symbols (HMMBW_E_INVALID otherwise).
+ * Any context (1 <= N <= 64, both topologies); a multi-rank context decodes its own shard, no collective.
+ * Leaves the log-likelihoods of hmmbw_get_loglik, the statistics and the training state as they were. */
+int hmmbw_viterbi(hmmbw_ctx *ctx, double *logp_out, int32_t *path_out, int64_t path_len);
 
 /* Engine knobs.  HMMBW_OPT_SAFE_SCALING = 1 forces the per-step power-of-two normalisation of the
  * forward recursion (default 0: lagged normalisation, automatic per-wave fallback to the per-step
