@@ -31,7 +31,16 @@
 // index) sums the rows of each symbol: deterministic, and HBM-streaming rather than atomic-bound.
 #pragma once
 
-#include "hmmbw_device.hpp"
+#include <hip/hip_runtime.h>
+
+#include <cmath>
+#include <cstdint>
+#include <type_traits>
+
+#include "hmmbw_args.hpp"
+#include "lane_ops.hpp"
+#include "mstep.hpp"  // the log-likelihood pairs: block_ll_partial, rank_ll_count, rank_ll_fold
+#include "phase_stamps.hpp"
 
 namespace hmmbw {
 
@@ -40,20 +49,11 @@ typedef double f64x4 __attribute__((ext_vector_type(4)));
 constexpr int kTileSeqs = 16;  // sequences per tile = MFMA columns
 // The gamma rows (1.28 GB per cfg5-shard iteration, written once by the E-step, read once by the gather)
 // move with nontemporal stores and loads: E-step + gather 1,714 -> 1,672 us (the gather 233 -> 193 us).
-#ifndef HMMBW_GAMMA_NT
-#define HMMBW_GAMMA_NT 1
-#endif
-// alpha_hat (written by the forward, read once by the backward) likewise: E-step 1,480-1,488 -> 1,476-1,481 us
+// alpha_hat (written by the forward, read once by the backward) likewise: E-step 1,480-1,488 -> 1,476-1,481 us.
 // The work queue hands alpha_hat and s_t from the forward unit to the backward unit with agent-scope
 // stores / loads (write-through past the non-coherent XCD L2s; the flag follows vmcnt(0)) instead of a
 // release fence (an XCD-wide L2 write-back per forward unit) and an acquire (an L2 invalidate per
 // backward unit): whole cfg5 11.78 -> 11.57 ms per iteration (profiles/r4/wide_work_queue_ab.txt).
-#ifndef HMMBW_WQ_WT
-#define HMMBW_WQ_WT 1
-#endif
-#ifndef HMMBW_ALPHA_NT
-#define HMMBW_ALPHA_NT 1
-#endif
 
 // Profiling ablations of the inner loops (results wrong by construction) exist only in a diagnostics
 // build (-DHMMBW_WIDE_ABLATE): a runtime test inside the step loops costs the release build its
@@ -143,15 +143,11 @@ __global__ void __launch_bounds__(NT * 64, 2) k_estep_mfma(EArgs a) {  // 2 wave
     const unsigned *gdw = a.gdst + (FWD_ONLY ? 0 : a.L.wave_ckoff[tile] / NP) + s;
     auto putg = [&](unsigned row, const f64x4 &v) HMMBW_AI {
         double2 *q = reinterpret_cast<double2 *>(a.gam + (long long)row * NP + col0);
-        if constexpr (HMMBW_GAMMA_NT) {  // written once here, read once by the gather
-            typedef double d2 __attribute__((ext_vector_type(2)));
-            d2 *qq = reinterpret_cast<d2 *>(q);
-            __builtin_nontemporal_store(d2{v[0], v[1]}, qq);
-            __builtin_nontemporal_store(d2{v[2], v[3]}, qq + 1);
-        } else {
-            q[0] = double2{v[0], v[1]};
-            q[1] = double2{v[2], v[3]};
-        }
+        // nontemporal: written once here, read once by the gather
+        typedef double d2 __attribute__((ext_vector_type(2)));
+        d2 *qq = reinterpret_cast<d2 *>(q);
+        __builtin_nontemporal_store(d2{v[0], v[1]}, qq);
+        __builtin_nontemporal_store(d2{v[2], v[3]}, qq + 1);
     };
 
     auto loadpack = [&](int c) HMMBW_AI -> uint4 {
@@ -274,16 +270,15 @@ __global__ void __launch_bounds__(NT * 64, 2) k_estep_mfma(EArgs a) {  // 2 wave
             if (!WIDE_ABL(a, 8)) {
 #pragma unroll
                 for (int r = 0; r < 4; ++r) {
-                    if constexpr (WQ && HMMBW_WQ_WT)
+                    if constexpr (WQ)
                         __hip_atomic_store(&ckw[((long long)t * NT * 4 + r) * 64], z[r], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                    else if constexpr (HMMBW_ALPHA_NT) __builtin_nontemporal_store(z[r], &ckw[((long long)t * NT * 4 + r) * 64]);
-                    else ckw[((long long)t * NT * 4 + r) * 64] = z[r];
+                    else __builtin_nontemporal_store(z[r], &ckw[((long long)t * NT * 4 + r) * 64]);
                 }
             }
             // every wave computes the same s_t from all NP states: one lane group stores it (STEADY: all
             // lanes, the same value to the same 16 words, so the store needs no exec branch)
             if (STEADY || (m == 0 && g == 0)) {
-                if constexpr (WQ && HMMBW_WQ_WT) __hip_atomic_store(&ew[t * kTileSeqs], sc, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                if constexpr (WQ) __hip_atomic_store(&ew[t * kTileSeqs], sc, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
                 else ew[t * kTileSeqs] = sc;
             }
         }
@@ -348,14 +343,11 @@ __global__ void __launch_bounds__(NT * 64, 2) k_estep_mfma(EArgs a) {  // 2 wave
         }
         __syncthreads();
         do_b = s_ok != 0;
-        if constexpr (!HMMBW_WQ_WT) __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
         if (do_b && Tw > 0) {
 #pragma unroll
             for (int r = 0; r < 4; ++r) {
                 const double *q = &ckw[((long long)(Tw - 1) * NT * 4 + r) * 64];
-                if constexpr (HMMBW_WQ_WT) z[r] = __hip_atomic_load(q, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                else if constexpr (HMMBW_ALPHA_NT) z[r] = __builtin_nontemporal_load(q);
-                else z[r] = *q;
+                z[r] = __hip_atomic_load(q, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
             }
         }
     }
@@ -419,7 +411,7 @@ __global__ void __launch_bounds__(NT * 64, 2) k_estep_mfma(EArgs a) {  // 2 wave
         f64x4 zs;  // z_t masked to the regular steps: gamma_t of the step that consumes the image
         f64x4 accn;  // beta of the next step to consume: its own-block MFMAs, issued by publish
         auto ldew = [&](int t) HMMBW_AI -> int {
-            if constexpr (WQ && HMMBW_WQ_WT) return __hip_atomic_load(&ew[t * kTileSeqs], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            if constexpr (WQ) return __hip_atomic_load(&ew[t * kTileSeqs], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
             else return ew[t * kTileSeqs];
         };
         auto ldz = [&](int t) HMMBW_AI -> f64x4 {
@@ -427,10 +419,9 @@ __global__ void __launch_bounds__(NT * 64, 2) k_estep_mfma(EArgs a) {  // 2 wave
             if (WIDE_ABL(a, 8)) return f64x4{0.5, 0.5, 0.5, 0.5};
 #pragma unroll
             for (int r = 0; r < 4; ++r) {
-                if constexpr (WQ && HMMBW_WQ_WT)
+                if constexpr (WQ)
                     v[r] = __hip_atomic_load(&ckw[((long long)t * NT * 4 + r) * 64], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                else if constexpr (HMMBW_ALPHA_NT) v[r] = __builtin_nontemporal_load(&ckw[((long long)t * NT * 4 + r) * 64]);
-                else v[r] = ckw[((long long)t * NT * 4 + r) * 64];
+                else v[r] = __builtin_nontemporal_load(&ckw[((long long)t * NT * 4 + r) * 64]);
             }
             return v;
         };
@@ -586,8 +577,7 @@ __global__ void __launch_bounds__(NT * 64, 2) k_estep_mfma(EArgs a) {  // 2 wave
         if (do_f) {  // the tile's log P pair, then the release of alpha_hat and s_t to its backward unit
             __syncthreads();
             block_ll_partial(lp, ll_valid, sRed + NT * kTileSeqs, a.llpart + 2 * tile);
-            if constexpr (HMMBW_WQ_WT) __builtin_amdgcn_s_waitcnt(0x0F70);  // vmcnt(0): the stores have landed
-            else __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
+            __builtin_amdgcn_s_waitcnt(0x0F70);  // vmcnt(0): the stores have landed
             __syncthreads();
             if (tid == 0) __hip_atomic_store(a.wq_flag + tile, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
         } else if (a.rank_ll != nullptr) {
@@ -660,8 +650,7 @@ __global__ void __launch_bounds__(256) k_bnum_gather(const double *gam, const un
 #pragma unroll
             for (int u = 0; u < U; ++u) {
                 const long long r = SORTED ? (pw + g + u < e ? pw + g + u : b) : (long long)__builtin_amdgcn_readlane(cur, g + u);
-                if constexpr (HMMBW_GAMMA_NT) x[u] = __builtin_nontemporal_load(&gam[r * NP + q]);
-                else x[u] = gam[r * NP + q];
+                x[u] = __builtin_nontemporal_load(&gam[r * NP + q]);
             }
 #pragma unroll
             for (int u = 0; u < U; ++u) acc += (pw + g + u < e) ? x[u] : 0.0;

@@ -1,5 +1,6 @@
 // estep_small_inst.hip — instantiates the small-N E-step / scorer kernels for N = HMMBW_INST_N
 // (the build compiles this file once per N = 1..16, in parallel).
+#include "hmmbw_device.hpp"
 #include "hmmbw_kernels.hpp"
 
 #ifndef HMMBW_INST_N
@@ -24,7 +25,7 @@ template <>
 Kernels small_kernels_n<HMMBW_INST_N>(bool lr, bool ldstab) {
     constexpr int N = HMMBW_INST_N;
     constexpr int G = N <= 2 ? 2 : (N <= 4 ? 4 : (N <= 8 ? 8 : 16));
-    const KernelFn join_split = JoinSplit<N, G, G == 8 && kTabPad == 0>::get(lr);
+    const KernelFn join_split = JoinSplit<N, G, G == 8>::get(lr);
     if (lr) {
         if (ldstab)
             return Kernels{k_estep_small<N, G, true, true, false>, k_estep_small<N, G, true, true, true>,

@@ -21,15 +21,23 @@
 //        row_shr/shl, row_half_mirror, row_mirror, row_newbcast); B^T and the B-numerator histogram
 //        in LDS; the forward sweep stores one alpha_hat checkpoint per 8-step chunk plus the int16
 //        scale exponents, the backward sweep recomputes each chunk's alpha_hat in registers
-//        (bit-identical) and fuses beta, gamma, xi and the histogram scatter.
-//   k_estep_wide<NP,FWD_ONLY>              16 < N <= 64: one sequence per wavefront, lane = state,
-//        A / A^T in LDS, alpha / v exchanged through a per-wave LDS row.
+//        (bit-identical) and fuses beta, gamma, xi and the histogram scatter (hmmbw_device.hpp).
+//   k_estep_join<N,G,LR,LAY>, k_estep_small_group<...>  the same body on the joined spread map (one
+//        8-wave workgroup per CU; LAY = 1: class-split LDS tables) and for several models in one launch.
+//   k_estep_mfma<NT,FWD_ONLY,DET,WQ>       16 < N <= 64: a workgroup owns a tile of 16 sequences, wave m
+//        the 16-state block m; the recursions and xi on the fp64 MFMA, the other waves' blocks through
+//        LDS (estep_mfma.hpp).  k_bnum_gather sums its gamma rows per symbol into the B numerator.
 //   k_reduce_local  (multi-rank) sum the statistics copies into the all-reduce buffer + the rank's
 //                   (max, sum exp) pair of log P_r.
+//   k_det_reduce    (deterministic mode) sum the per-workgroup partial statistics in workgroup order.
 //   k_mstep / k_mstep_staged  one workgroup: L, M-step, convergence record, zero the statistics
 //                   (staged: all statistics gathered into LDS with one batch of loads).
 //   k_mstep_grid    large N x K (wide path): B re-estimated by the whole grid, the rest by workgroup 0.
+//                   (Their bodies: mstep.hpp; merged into the next E-step launch: merged_mstep.)
+//   k_snapshot      the state and the iteration records into pinned host memory (hmmbw_status_post).
 //   k_finalise  the reference's return-path normalisation (:524-541).
+//   k_init_state    the convergence state of a new run.
+//   (peer.hip, viterbi.hip and vq.hip hold their own kernels.)
 //
 // Host units (host.hpp): this one holds the context's life cycle, observations, options and parameters,
 // the launch planner, hmmbw_estep / _mstep / _iterate*, status, scoring and timing; alloc.hip the block
@@ -40,6 +48,7 @@
 #include <mutex>
 
 #include "host.hpp"
+#include "mstep.hpp"
 
 namespace hmmbw {
 
@@ -85,7 +94,7 @@ __global__ void __launch_bounds__(256) k_det_reduce(const double *part, long lon
 
 __global__ void __launch_bounds__(256) k_mstep(MArgs m) {
     if (carry_if_done(m)) return;
-    mstep_block<false>(m);
+    mstep_block(m);
 }
 
 __global__ void __launch_bounds__(256) k_mstep_grid(MArgs m) {
@@ -97,7 +106,7 @@ __global__ void __launch_bounds__(256) k_mstep_grid(MArgs m) {
 __global__ void __launch_bounds__(256) k_mstep_staged(MArgs m) {
     extern __shared__ double sSt[];
     if (carry_if_done(m)) return;
-    mstep_staged<false>(m, sSt);
+    mstep_staged(m, sSt);
 }
 
 // Status snapshot for hmmbw_status_post: the state record and the iteration records [first, iteration)
@@ -417,7 +426,7 @@ static int launch_lds(F f, unsigned grid, size_t lds, hipStream_t stream, const 
 // as soon as observations and a dense A are both known (set_observations / set_params), so an
 // out-of-memory surfaces there rather than in the first training call.
 static int ensure_zf(hmmbw_ctx *c) {
-    if (!HMMBW_ZFULL || c->wide || !c->has_obs || !c->has_params || c->topo == HMMBW_TOPOLOGY_LEFT_TO_RIGHT || c->d_zf)
+    if (c->wide || !c->has_obs || !c->has_params || c->topo == HMMBW_TOPOLOGY_LEFT_TO_RIGHT || c->d_zf)
         return HMMBW_OK;
     if (int rc = dalloc(&c->d_zf, (size_t)std::max(c->cktot * kChunk, 1LL)))
         return fail(rc, "dense A: the forward's every-step store (" + std::to_string(8 * c->cktot * kChunk) +
@@ -516,7 +525,7 @@ int plan_estep(hmmbw_ctx *c, bool fwd_only, const IterState *state, double *copi
                 }
             }
             a.split_extra = split_extra_on(c->map, c->topo, p.block == 2 * kBlock) ? 1 : 0;
-            if (HMMBW_ZFULL && !lr && !fwd_only) {  // dense: the forward stores every z_t (hmmbw_device.hpp)
+            if (!lr && !fwd_only) {  // dense: the forward stores every z_t (hmmbw_device.hpp)
                 if (int rc = ensure_zf(c)) return rc;
                 a.ckpt = c->d_zf;
             }
@@ -811,7 +820,7 @@ int hmmbw_set_observations(hmmbw_ctx *c, const int64_t *offsets, const int32_t *
     const int64_t total = offsets[R];
     // packs hold LDS byte offsets of the emission record rows when the tables live in LDS (< 64 KiB,
     // so they fit uint16), symbol ids otherwise
-    const long long row_bytes = (long long)(c->G + kTabPad) * 16;  // 16-B table entries
+    const long long row_bytes = (long long)c->G * 16;  // 16-B table entries
     std::vector<uint16_t> hsym = fill_packs(L, offsets, symbols, c->lds_tables() ? row_bytes : 1);
     free_obs(c);
 

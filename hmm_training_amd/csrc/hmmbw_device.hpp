@@ -1,440 +1,26 @@
-// hmmbw_device.hpp — device code of the MI355X Baum-Welch engine (kernels, reductions, M-step
-// building blocks), shared by the host translation unit (hmmbw.hip) and the per-N instantiation
-// units (estep_small_inst.hip, estep_wide_inst.hip) that the build compiles in parallel.
+// hmmbw_device.hpp — the small-N (N <= 16) E-step / scorer of the MI355X Baum-Welch engine: its LDS emission
+// tables, the merged M-step prologue that fills them, estep_small_body and the three k_estep_small* kernels.
+// Instantiated per N by estep_small_inst.hip.  The pieces it is built from: hmmbw_args.hpp (the argument structs,
+// all the host units see of the device side), phase_stamps.hpp (diagnostics builds), lane_ops.hpp (cross-lane
+// helpers), mstep.hpp (the M-step's shared arithmetic and the log-likelihood folds).
 // See hmmbw.hip for the kernel map and DESIGN.md for the numerics.
 #pragma once
 #include <hip/hip_runtime.h>
 
-#include <algorithm>
+#include <climits>
 #include <cmath>
 #include <cstdint>
-#include <cstdio>
-#include <cstring>
-#include <numeric>
-#include <string>
 #include <type_traits>
-#include <vector>
 
+#include "hmmbw_args.hpp"
+#include "lane_ops.hpp"
 #include "lds_layout.hpp"
-#include "obs_plan.hpp"
-
-#include "../../include/hmmbw.h"
+#include "mstep.hpp"
+#include "phase_stamps.hpp"
 
 namespace hmmbw {
 
-// Diagnostics build only (-DHMMBW_PHASE_TIMES, tools/phase_times.py): per-wave wall-clock stamps of
-// the small E-step's phases, read back with hmmbw_debug_phase_times.
-#ifdef HMMBW_PHASE_TIMES
-constexpr int kPhaseWaves = 1 << 16;
-constexpr int kPhaseSlots = 16;
-static __device__ unsigned long long g_phase[kPhaseWaves][kPhaseSlots];
-#define PHASE(k)                                                                               \
-    do {                                                                                       \
-        const long long w_ = (long long)blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6);   \
-        if ((threadIdx.x & 63) == 0 && w_ < kPhaseWaves) g_phase[w_][k] = wall_clock64();      \
-    } while (0)
-// diagnostics: where the wave runs: HW_ID (wave, SIMD, CU, shader array, engine fields) in slot 15, XCC_ID
-// in slot 14
-#define PHASE_HWID()                                                                                    \
-    do {                                                                                                \
-        const long long w_ = (long long)blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6);            \
-        if ((threadIdx.x & 63) == 0 && w_ < kPhaseWaves) {                                              \
-            g_phase[w_][15] = (unsigned)__builtin_amdgcn_s_getreg((31 << 11) | 4);                      \
-            g_phase[w_][14] = (unsigned)__builtin_amdgcn_s_getreg((15 << 11) | 20);                     \
-        }                                                                                               \
-    } while (0)
-// diagnostics: wait for every outstanding memory operation of the wave, then stamp
-#define PHASE_DRAIN(k)                   \
-    do {                                 \
-        __builtin_amdgcn_s_waitcnt(0);   \
-        PHASE(k);                        \
-    } while (0)
-// shader-clock stamp at the start of forward (d = 0) / backward (d = 1) chunk c (c < 64); only with
-// -DHMMBW_CHUNK_TIMES too: its conditional stores inside the sweeps change their s_waitcnt placement
-static __device__ unsigned long long g_chunk[4096][2][64];
-#ifdef HMMBW_CHUNK_TIMES
-#define CHUNKSTAMP(d, c)                                                                       \
-    do {                                                                                       \
-        const long long w_ = (long long)blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6);   \
-        if ((threadIdx.x & 63) == 0 && w_ < 4096 && (c) < 64) g_chunk[w_][d][c] = clock64();   \
-    } while (0)
-#else
-#define CHUNKSTAMP(d, c) \
-    do {                 \
-    } while (0)
-#endif
-#else
-#define CHUNKSTAMP(d, c) \
-    do {                 \
-    } while (0)
-#define PHASE(k) \
-    do {         \
-    } while (0)
-#define PHASE_HWID() \
-    do {             \
-    } while (0)
-#define PHASE_DRAIN(k) \
-    do {               \
-    } while (0)
-#endif
-
-// 1: the dense path's stored z_t (written once, read once) nontemporal.  Measured worse (cfg3 dense 79.7-80.5
-// against 73.6-73.8 us): the backward reads them back while the caches still hold them.
-#ifndef HMMBW_ZF_NT
-#define HMMBW_ZF_NT 0
-#endif
-
-// kWave, kChunk, kBlock: obs_plan.hpp
-#ifndef HMMBW_KSCALE
-#define HMMBW_KSCALE 8
-#endif
-constexpr int kScale = HMMBW_KSCALE;  // lagged mode: the forward rescales every kScale steps
-constexpr int kHist = 4096;
-
-struct IterState {
-    double prev_L;
-    double last_L;
-    double last_diff;
-    double epsilon;
-    long long iteration;
-    long long max_iterations;
-    int done;
-    int converged;
-    int error;      // HMMBW_E_* of a device-side failure; done is set with it
-    int error_src;  // which bounded wait failed: kErrPeer (peer all-reduce) or kErrWorkQueue (wide work queue)
-};
-constexpr int kErrPeer = 1;
-constexpr int kErrWorkQueue = 2;
-
-// Observation layout in HBM (built once by hmmbw_set_observations).
-//   slot = wave * U + u  ->  caller sequence slot_seq[slot] (-1: padding), length slot_len[slot]
-//   sym    : per wave, chunk-major [chunk][u][8] uint16  (one 16-B load = 8 steps of one sequence)
-//   ckpt   : per wave [chunk][64 lanes] fp64 — alpha_hat at the first step of every chunk (small N)
-//   spack  : per wave [chunk][u] 8 x int16 — the power-of-two scale exponent of every step
-//   alpha  : per wave [t][64 lanes] fp64 + ebuf [t][u] int32 — full alpha_hat (wide kernel only)
-struct Layout {
-    const uint16_t *sym;
-    const long long *wave_symoff;
-    const long long *wave_ckoff;   // doubles (small) | alpha doubles (wide)
-    const long long *wave_spoff;   // uint4 units (small) | ebuf ints (wide)
-    const int *wave_T;
-    const int *wave_full;          // 1: every real slot of the wave has length wave_T
-    const int *slot_len;
-    const int *slot_seq;
-    long long nwaves;
-};
-
-// Host-visible mirror of the convergence state (HMMBW_OPT_LIVE_STATUS), in fine-grained pinned host
-// memory: every M-step that records an iteration also writes the record and the new state here with
-// write-through stores, then publishes pub = epoch << 32 | iteration.  The state goes to slot
-// iteration % 2, so a reader that sees pub unchanged around its copy of that slot read one record.
-struct LiveBlock {
-    unsigned long long pub;
-    unsigned long long pad_[7];
-    IterState slot[2];
-    double hist[2 * kHist];  // (L, diff) of iteration i at 2 (i % kHist)
-};
-
-struct MArgs {
-    const double *src;     // statistics: the copies (single rank) or the all-reduced buffer
-    double *zero_ll;       // LL slots to clear (multi-rank) or nullptr
-    int nsrc;
-    long long copy_len;
-    double *pi, *A, *B, *Bt;
-    const double *llpart;
-    long long nblocks;
-    long long R_global;
-    const IterState *state;  // convergence state entering this M-step
-    IterState *state_out;    // ... and after it (double-buffered: the host flips the slots per M-step)
-    double *hist;
-    int N, K, G, world;
-    int local_lse;
-    int bt_perm;           // 1: B^T columns in the wide kernels' order (wide_col)
-    long long off_S, off_gex, off_gall, off_bnum, off_ll;
-    LiveBlock *live;       // HMMBW_OPT_LIVE_STATUS: the host mirror (or nullptr)
-    unsigned live_epoch;   // the host's reset count: records of an earlier run never match
-};
-
-struct EArgs {
-    Layout L;
-    const double *pi;
-    const double *A;
-    const double *Bt;  // [K][G] + G zero pad
-    double *ckpt;      // small: checkpoints | wide: alpha_hat
-    double *gam;       // wide: gamma rows [position][NP] (bt_col order) for k_bnum_gather
-    const unsigned *gdst;  // wide: row of position (tile row = wave_ckoff / NP + t * 16 + s) in symbol order
-    uint4 *spack;      // small: scale exponents
-    int *ebuf;         // wide: scale exponents
-    double *copies;    // [ncopies][copy_len] statistics accumulators (workgroup b adds into copy b % ncopies)
-    long long copy_len;
-    int ncopies;
-    double *logp;
-    double *llpart;    // [blocks][2]: per-block (max, sum exp) of log P
-    const IterState *state;
-    int K;
-    int N;
-    int force_safe;    // 1: per-step normalisation (no lagged scaling)
-    int ablate;        // diagnostics only: bit 0 skips the statistics flush, bit 1 the backward sweep
-    int merged;        // 1: run the previous iteration's M-step (m) in the prologue of every workgroup
-    double *zero;      // statistics buffer of the NEXT iteration, cleared by this launch (or nullptr)
-    long long zero_len;
-    double *part;      // deterministic mode: per-workgroup partial statistics [blocks][off_bnum]
-    double *rank_ll;   // multi-rank fused: this rank's (max, sum exp) slot in the all-reduce buffer (or nullptr)
-    int *done_ctr;     // ... and the workgroup completion counter that picks the workgroup forming it
-    MArgs m;
-    long long off_S, off_gex, off_gall, off_bnum;
-    // wave -> workgroup map of the small kernels: workgroups [0, nfull) run 4 sequence-group waves each,
-    // the workgroups after them only xact (the waves beyond one per SIMD spread over more CUs)
-    long long nfull;
-    int xact;
-    // wave priority (HMMBW_PRIO overrides): 2 (default) = s_setprio 1 for the spread map's extra waves, the
-    // second wave on their SIMDs (cfg3 34.5-34.7 us per iteration against 36.0-36.8 at 0, two interleaved
-    // rounds; no effect without extra waves, e.g. 12,500 sequences); 1 = for the full workgroups' waves
-    int prio;
-    // split extra waves (small kernels, LDS tables): the idle waves of the spread map's extra workgroups run
-    // the lower half of their partner's backward sweep (estep_small_body, "split"); 0 off
-    int split_extra;
-    // wide work queue (k_estep_mfma<..., WQ>): [0] next unit, [1] workgroups done; per-tile forward flags
-    unsigned *wq;
-    unsigned *wq_flag;
-    int wq_units;  // tiles
-    long long wq_timeout_ticks;  // bound (wall-clock ticks) of a backward unit's wait for its forward
-};
-
-// Grouped launch (k_estep_small_group): per-model arguments and first workgroups (start[nm] = grid)
-struct GroupArgs {
-    const EArgs *__restrict__ args;
-    const long long *__restrict__ start;
-    int nm;
-};
-
-// ---------------------------------------------------------------------------------------------
-// Cross-lane helpers (DPP on gfx950; 64-bit operands are split or use v_mov_b64_dpp)
-// ---------------------------------------------------------------------------------------------
-template <int CTRL>
-__device__ __forceinline__ double dpp(double v) {
-    long long x = __builtin_bit_cast(long long, v);
-    x = __builtin_amdgcn_update_dpp(0ll, x, CTRL, 0xF, 0xF, true);
-    return __builtin_bit_cast(double, x);
-}
-
-template <int CTRL>
-__device__ __forceinline__ int dpp_i32(int v) {
-    return __builtin_amdgcn_update_dpp(0, v, CTRL, 0xF, 0xF, true);
-}
-
-// lane ^ 16 / lane ^ 32 partners of a double without LDS: v_permlane16_swap / v_permlane32_swap (VALU) on
-// both halves.  Each returns (own, partner) in an order that depends on the row, so combine the pair with a
-// commutative operation only (every lane of the pair then gets the bitwise-identical result).
-template <bool P32>
-__device__ __forceinline__ void swap_pair(double v, double &a, double &b) {
-    const unsigned lo = (unsigned)__double2loint(v), hi = (unsigned)__double2hiint(v);
-    const auto l = P32 ? __builtin_amdgcn_permlane32_swap(lo, lo, false, false)
-                       : __builtin_amdgcn_permlane16_swap(lo, lo, false, false);
-    const auto h = P32 ? __builtin_amdgcn_permlane32_swap(hi, hi, false, false)
-                       : __builtin_amdgcn_permlane16_swap(hi, hi, false, false);
-    a = __hiloint2double((int)h[0], (int)l[0]);
-    b = __hiloint2double((int)h[1], (int)l[1]);
-}
-template <bool P32>
-__device__ __forceinline__ double add_swap(double v) {
-    double a, b;
-    swap_pair<P32>(v, a, b);
-    return a + b;
-}
-template <bool P32>
-__device__ __forceinline__ double max_swap(double v) {
-    double a, b;
-    swap_pair<P32>(v, a, b);
-    return fmax(a, b);
-}
-
-// Sum over a group of G lanes (butterfly; every lane gets the bitwise-identical result because
-// each level adds the same two partial sums, only commuted).  No LDS round trip: DPP within a row,
-// permlane swaps across rows (round 6: the ds_bpermute of __shfl_xor cost ~120 cycles per level).
-template <int G>
-__device__ __forceinline__ double gsum(double x) {
-    if constexpr (G >= 2) x += dpp<0xB1>(x);   // quad_perm [1,0,3,2]
-    if constexpr (G >= 4) x += dpp<0x4E>(x);   // quad_perm [2,3,0,1]
-    if constexpr (G >= 8) x += dpp<0x141>(x);  // row_half_mirror
-    if constexpr (G >= 16) x += dpp<0x140>(x); // row_mirror
-    if constexpr (G >= 32) x = add_swap<false>(x);
-    if constexpr (G >= 64) x = add_swap<true>(x);
-    return x;
-}
-
-// Sum over the lanes of a wave that share (lane mod G), e.g. the U sequences of a G-lane-group layout: the
-// result is complete in every lane (the order of the additions may differ between lanes).
-template <int G>
-__device__ __forceinline__ double usum(double x) {
-    if constexpr (G <= 2) x += __shfl_xor(x, 2);
-    if constexpr (G <= 4) x += dpp<0x124>(x);   // row_ror:4
-    if constexpr (G <= 8) x += dpp<0x128>(x);   // row_ror:8
-    if constexpr (G <= 16) x = add_swap<false>(x);
-    return add_swap<true>(x);
-}
-
-// min over the lanes of a wave that share (lane mod G), ints (DPP in the row, permlane swaps across rows)
-template <int G>
-__device__ __forceinline__ int umin_i32(int x) {
-    if constexpr (G <= 2) x = min(x, __shfl_xor(x, 2));
-    if constexpr (G <= 4) x = min(x, dpp_i32<0x124>(x));  // row_ror:4
-    if constexpr (G <= 8) x = min(x, dpp_i32<0x128>(x));  // row_ror:8
-    if constexpr (G <= 16) {
-        const auto r = __builtin_amdgcn_permlane16_swap((unsigned)x, (unsigned)x, false, false);
-        x = min((int)r[0], (int)r[1]);
-    }
-    const auto r = __builtin_amdgcn_permlane32_swap((unsigned)x, (unsigned)x, false, false);
-    return min((int)r[0], (int)r[1]);
-}
-
-template <int G>
-__device__ __forceinline__ int gmax_i32(int e) {
-    if constexpr (G >= 2) e = max(e, dpp_i32<0xB1>(e));
-    if constexpr (G >= 4) e = max(e, dpp_i32<0x4E>(e));
-    if constexpr (G >= 8) e = max(e, dpp_i32<0x141>(e));
-    if constexpr (G >= 16) e = max(e, dpp_i32<0x140>(e));
-    return e;
-}
-
-// Exponent that steers the power-of-two scaling: frexp exponent of the group's largest entry
-// (entries are >= 0), kZeroExp when the whole group is zero.
-constexpr int kZeroExp = -8192;
-template <int G>
-__device__ __forceinline__ int group_exp(double z) {
-    return gmax_i32<G>(z > 0.0 ? __builtin_amdgcn_frexp_exp(z) : kZeroExp);
-}
-
-// Value of lane I of this lane's G-group.
-template <int G, int I>
-__device__ __forceinline__ double gbcast(double v, int lane) {
-    if constexpr (G == 2) {
-        return dpp<(I) | ((I) << 2) | ((2 + I) << 4) | ((2 + I) << 6)>(v);
-    } else if constexpr (G == 4) {
-        return dpp<(I) * 0x55>(v);
-    } else if constexpr (G == 8) {
-        const double lo = dpp<0x150 + I>(v);
-        const double hi = dpp<0x150 + 8 + I>(v);
-        return (lane & 8) ? hi : lo;
-    } else {
-        static_assert(G == 16, "group size");
-        return dpp<0x150 + I>(v);  // row_newbcast:I
-    }
-}
-
-template <int B, int E, class F>
-__device__ __forceinline__ void sfor(F &&f) {
-    if constexpr (B < E) {
-        f(std::integral_constant<int, B>{});
-        sfor<B + 1, E>(f);
-    }
-}
-
-// Dense-A cross-lane products with the broadcast fused into the multiply-add: gfx950's 64-bit DPP
-// ("DP ALU DPP") has only row_newbcast, which broadcasts lane L of every 16-lane row, so for G-lane
-// groups (G = 4, 8, 16) one v_fmac_f64_dpp per group position Q, with bank_mask restricting the write
-// to that group's lanes, gives  acc += z(lane I of this lane's group) * a  in 16 / G instructions, in
-// place of a broadcast, a select and an fma per group (the compiler does not fuse 64-bit DPP moves).
-template <int G, int I, int Q>
-__device__ __forceinline__ void fmac_bcast1(double &acc, double z, double a) {
-    constexpr int lane = Q * G + I;
-    constexpr int bm = ((1 << (G / 4)) - 1) << (Q * G / 4);
-    asm volatile("v_fmac_f64_dpp %0, %1, %2 row_newbcast:%3 row_mask:0xf bank_mask:%4"
-                 : "+v"(acc) : "v"(z), "v"(a), "i"(lane), "i"(bm));
-}
-// VALU write -> DPP read of that VGPR needs 2 wait states; the compiler does not see the DPP read
-// inside the asm, so the first fused product after z is written goes behind this.
-__device__ __forceinline__ void dpp_guard(double z) { asm volatile("s_nop 1" ::"v"(z)); }
-
-// acc0 += sum over even i of a[i] z(lane i), acc1 the odd i (two chains), per G-lane group.  (Four
-// chains, i mod 4, measured slower at dense cfg3: 76-77 against 71-73 us, profiles/r5/ab_dense_dot4.txt.)
-template <int G, int N>
-__device__ __forceinline__ void bcast_dot(double &acc0, double &acc1, double z, const double (&a)[N]) {
-    dpp_guard(z);
-    sfor<0, (N + 1) / 2>([&](auto P) {
-        constexpr int i0 = 2 * decltype(P)::value, i1 = i0 + 1;
-        sfor<0, 16 / G>([&](auto Q) {
-            fmac_bcast1<G, i0, decltype(Q)::value>(acc0, z, a[i0]);
-            if constexpr (i1 < N) fmac_bcast1<G, i1, decltype(Q)::value>(acc1, z, a[i1]);
-        });
-    });
-}
-
-// Dense xi partial sums of a G = 8 wave (lane = 8 u + j) on the 4x4x4 f64 MFMA: its block is lane
-// bits 2-3, A lane 16k + 4blk + m holds A[m][k], B lane 16k + 4blk + n holds B[k][n], D lane
-// 16m + 4blk + n holds D[m][n] (tools/ubench_mfma4.hip, profiles/r3/ubench_mfma4x4x4.txt).  With
-// z as A and v as B, block (j >> 2, u & 1) sums over the seqs u >> 1:
-//   X[0] lane 16m + 4jh + 8u0 + n:  sum z_t(4jh + m) v_{t+1}(4jh + n)            (diagonal 4x4 blocks)
-//   X[1] with v row_half_mirrored (state j -> 7 - j):  ... v_{t+1}(4(1 - jh) + 3 - n)  (off-diagonal)
-// The accumulation is off the forward/backward chains, so the MFMA's ~44-cycle SrcC latency is
-// hidden; it replaces 16 v_fmac_f64_dpp per step (bcast_acc).
-__device__ __forceinline__ void xi_mfma8(double (&X)[2], double zs, double vd) {
-    X[0] = __builtin_amdgcn_mfma_f64_4x4x4f64(zs, vd, X[0], 0, 0, 0);
-    X[1] = __builtin_amdgcn_mfma_f64_4x4x4f64(zs, dpp<0x141>(vd), X[1], 0, 0, 0);  // row_half_mirror
-}
-
-// S[i] += z(lane i) * w for every state i of the group
-template <int G, int N, int NS>
-__device__ __forceinline__ void bcast_acc(double (&S)[NS], double z, double w) {
-    dpp_guard(z);
-    sfor<0, 16 / G>([&](auto Q) {
-        sfor<0, N>([&](auto I) { fmac_bcast1<G, decltype(I)::value, decltype(Q)::value>(S[decltype(I)::value], z, w); });
-    });
-}
-
-__device__ __forceinline__ int sym_of(const uint4 &p, int s) {
-    const unsigned w = s < 2 ? p.x : (s < 4 ? p.y : (s < 6 ? p.z : p.w));
-    return (s & 1) ? int(w >> 16) : int(w & 0xFFFFu);
-}
-
-__device__ __forceinline__ int exp_of(const uint4 &p, int s) {  // signed int16 lanes of a pack
-    const unsigned w = s < 2 ? p.x : (s < 4 ? p.y : (s < 6 ? p.z : p.w));
-    return (s & 1) ? int((int)w >> 16) : int((int)(w << 16) >> 16);
-}
-
-__device__ __forceinline__ uint4 pack_exps(const int *e) {
-    uint4 p;
-    p.x = (unsigned)(e[0] & 0xFFFF) | ((unsigned)e[1] << 16);
-    p.y = (unsigned)(e[2] & 0xFFFF) | ((unsigned)e[3] << 16);
-    p.z = (unsigned)(e[4] & 0xFFFF) | ((unsigned)e[5] << 16);
-    p.w = (unsigned)(e[6] & 0xFFFF) | ((unsigned)e[7] << 16);
-    return p;
-}
-
-__device__ __forceinline__ double pow2_scale(double x, int e) { return __builtin_amdgcn_ldexp(x, -e); }
-
-// 32-bit LDS byte address of a pointer into shared memory, and back (kept in one VGPR instead of
-// being re-derived from its parts)
-typedef __attribute__((address_space(3))) char lds_char;
-__device__ __forceinline__ unsigned lds_addr(const char *p) {
-    return (unsigned)(size_t)(const lds_char *)p;
-}
-__device__ __forceinline__ char *lds_ptr(unsigned a) {
-    return (char *)(lds_char *)(size_t)a;
-}
-
-// Per-block (max, sum exp(x - max)) of the sequences' log P (each sequence contributes from
-// exactly one lane with valid = true).  All threads of the block call it.
-__device__ __forceinline__ double wave_max(double x);
-__device__ __forceinline__ void block_ll_partial(double lp, bool valid, double *sh, double *out) {
-    const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6, nw = blockDim.x >> 6;
-    double m = wave_max(valid ? lp : -INFINITY);
-    if (lane == 0) sh[wv] = m;
-    __syncthreads();
-    double M = -INFINITY;
-    for (int w = 0; w < nw; ++w) M = fmax(M, sh[w]);
-    const double s = gsum<64>((valid && M != -INFINITY && lp != -INFINITY) ? exp(lp - M) : 0.0);
-    __syncthreads();
-    if (lane == 0) sh[wv] = s;
-    __syncthreads();
-    if (tid == 0) {
-        double S = 0.0;
-        for (int w = 0; w < nw; ++w) S += sh[w];
-        // memory-side atomics: the fused M-step of the last workgroup reads these with atomics too
-        atomicExch(&out[0], (S > 0.0) ? M : 0.0);
-        atomicExch(&out[1], S);
-    }
-}
+constexpr int kScale = 8;  // lagged mode: the forward rescales every kScale steps
 
 // ---------------------------------------------------------------------------------------------
 // Small-N E-step / scorer.  One G-lane group per sequence (lane j = state j), 64/G per wave.
@@ -454,43 +40,25 @@ __device__ __forceinline__ void block_ll_partial(double lp, bool valid, double *
 //   gamma_t(i) = z_t(i) beta_hat_t(i),  xi_t(i,j) = a_ij z_t(i) v_j  (accumulated as S_ij = xi/a_ij).
 // gamma is scattered into the per-workgroup LDS histogram B_num[o_t][j] (ds_add_f64).
 // ---------------------------------------------------------------------------------------------
-// LDS emission tables of the small kernels: two [K x GP] tables of 16-byte entries (GP = G + kTabPad
-// columns, the columns past N zero), the second kHistOff bytes after the first:
+// LDS emission tables of the small kernels: two [K x G] tables of 16-byte entries (the columns past N
+// zero), the second kHistOff bytes after the first (lds_layout.hpp: kHistOff, lds_tables_fit):
 //   P-table {x, y}: left-to-right x = a_jj b_j(o), y = a_{j-1,j} b_j(o) (the two products of the
 //                   forward step); dense x = b_j(o), y = 0;
 //   H-table {h, b}: h = the workgroup's B-numerator histogram (hmm_training.py:474-485), b = b_j(o).
-// The symbol packs hold the byte offset of the symbol's row, o * GP * 16, so ONE lane address per step
+// The symbol packs hold the byte offset of the symbol's row, o * G * 16, so ONE lane address per step
 // serves the emission read (ds_read_b128, offset 0) and the histogram add (ds_add_f64, offset
 // kHistOff): the constant distance is the instructions' immediate offset.
-// Rows are 8 x 16 B for G = 8 (no pad column): a ds_read_b128 lane group (4 windows of 4 states of 4
+// Rows are 8 x 16 B for G = 8, with no pad column: a ds_read_b128 lane group (4 windows of 4 states of 4
 // sequences) then meets 1.74 bank conflicts per 16 lanes on uniform symbols, against 2.44 with a pad
 // column (simulated with the MI355X_MICROARCH.md grouping; tools/lds_banks.py).  Padding slots of
 // ragged waves read row 0 (any finite entry: their steps are masked and add 0 to the histogram).
-#ifndef HMMBW_TAB_PAD
-#define HMMBW_TAB_PAD 0
-#endif
-constexpr int kTabPad = HMMBW_TAB_PAD;
-#ifndef HMMBW_XI_MFMA
-#define HMMBW_XI_MFMA 1
-#endif
-#ifndef HMMBW_ZFULL
-#define HMMBW_ZFULL 1
-#endif
-#ifndef HMMBW_FLUSH_VMWAIT  // explicit vmcnt(0) before the histogram flush (round 6 A/B)
-#define HMMBW_FLUSH_VMWAIT 1
-#endif
-#ifndef HMMBW_SPLIT_LR  // split extra waves in the left-to-right kernels too (the host enables them on the joined map)
-#define HMMBW_SPLIT_LR 1
-#endif
-#ifndef HMMBW_KARG_TOUCH  // touch every line of the kernel arguments at entry, in one batch (round 6 A/B)
-#define HMMBW_KARG_TOUCH 1
-#endif
+// (The class-split layout, LAY = 1, of the joined map's G = 8 kernels: lds_layout.hpp.)
 
-// The prologue reads the kernel arguments in several dependent rounds (the zero loop's, then the M-step's, then
-// the launch map's), and the first read of each 64-B line of the argument segment misses the scalar cache:
-// ~0.4 us per round at cfg3 (phase stamps, profiles/r6/phase_lr_cfg3.json).  One load per line, all issued
-// before the first wait, makes it one miss latency: LR cfg3 29.72 -> 29.62 us, T = 8 13.69 -> 13.56
-// (profiles/r6/prologue_ab.txt).
+// Touch every line of the kernel arguments at entry, in one batch.  The prologue reads the arguments in several
+// dependent rounds (the zero loop's, then the M-step's, then the launch map's), and the first read of each 64-B
+// line of the argument segment misses the scalar cache: ~0.4 us per round at cfg3 (phase stamps,
+// profiles/r6/phase_lr_cfg3.json).  One load per line, all issued before the first wait, makes it one miss
+// latency: LR cfg3 29.72 -> 29.62 us, T = 8 13.69 -> 13.56 (profiles/r6/prologue_ab.txt).
 template <class Args>
 __device__ __forceinline__ void touch_kernargs() {
     typedef const __attribute__((address_space(4))) unsigned karg_u32;
@@ -501,11 +69,6 @@ __device__ __forceinline__ void touch_kernargs() {
     for (int i = 0; i < n; ++i) acc ^= p[i * 16];
     asm volatile("" ::"s"(acc));
 }
-constexpr int kHistOff = kTabPad ? 40960 : 32768;
-__host__ __device__ constexpr bool lds_tables_fit(int K, int GP) { return (size_t)K * GP * 16 <= (size_t)kHistOff; }
-__host__ __device__ constexpr size_t lds_table_bytes(int K, int GP) { return (size_t)kHistOff + (size_t)K * GP * 16; }
-
-// (the class-split layout, LAY = 1, of the joined map's G = 8 kernels: lds_layout.hpp)
 
 // Entry i = k * GP + c (symbol k, state column c) of the LDS emission tables, 16 B each:
 // P {a_cc b_c(k), a_{c-1,c} b_c(k)} (left-to-right, PT) or {b_c(k), 0} (dense); H {histogram, b_c(k)}.
@@ -532,11 +95,188 @@ __device__ __forceinline__ void tab_put(double *sP, double *sH, int i, double px
     }
 }
 
-template <int N, int G, int GP, bool PT, int BLK = kBlock, int LAY = 0>
-__device__ __forceinline__ bool merged_mstep(const EArgs &a, double *sP, double *sH, double *sPA, long long bid);
-__device__ __forceinline__ int rank_ll_count(const EArgs &a);
-__device__ __forceinline__ void rank_ll_fold(const EArgs &a, long long nblk);
-__device__ __forceinline__ void ll_merge(double &M, double &S, double m2, double s2);
+// The previous iteration's M-step + convergence step (hmm_training.py:415-514), run by EVERY
+// workgroup of the merged E-step launch, straight into its LDS tables: every workgroup reads the same
+// statistics and log-likelihood pairs and applies the same arithmetic in the same order, so all of
+// them hold bit-identical parameters and reach the same stop decision.  Workgroup 0 also writes the
+// parameters back to HBM (for the queries) and records the iteration in the other state slot.
+// Returns false when EM stops here (or had stopped before).
+template <int N, int G, int GP, bool PT, int BLK, int LAY>
+__device__ __forceinline__ bool merged_mstep(const EArgs &a, double *sP, double *sH, double *sPA, long long bid) {
+    constexpr int NSM = N + N * N + 2 * N;  // pi_num, xi, gamma_den_excl, gamma_den_all
+    constexpr int NW = BLK / 64;
+    constexpr int SB = kMergedMaxStats / BLK;
+    constexpr int PB = 2;                   // log-likelihood pairs per thread per pass
+    __shared__ double sSm[NSM];
+    __shared__ double sMx[NW], sSum[NW];
+    __shared__ double sLr;  // multi-rank: L from the per-rank pairs (lse_rank_pairs)
+    __shared__ IterState sIn;
+    const MArgs &m = a.m;
+    const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
+    const int K = a.K;
+    const long long len = m.copy_len;
+    PHASE(8);
+    // ---- every load issued before any use: statistics, log-likelihood pairs, convergence state (the
+    // pairs and the state before the other copies' statistics are waited for: one latency, not two) ----
+    double v[SB];
+#pragma unroll
+    for (int q = 0; q < SB; ++q) {
+        const long long idx = (long long)q * BLK + tid;
+        v[q] = m.src[idx < len ? idx : len - 1];
+    }
+    const long long nb = m.nblocks;  // >= 1
+    double pm[PB], ps[PB];
+#pragma unroll
+    for (int q = 0; q < PB; ++q) {
+        const long long r = (long long)q * BLK + tid;
+        const long long rc = r < nb ? r : nb - 1;
+        pm[q] = m.llpart[2 * rc];
+        ps[q] = m.llpart[2 * rc + 1];
+    }
+    IterState in{};
+    if (tid == 0) {
+        in.prev_L = m.state->prev_L;
+        in.epsilon = m.state->epsilon;
+        in.iteration = m.state->iteration;
+        in.max_iterations = m.state->max_iterations;
+        in.done = m.state->done;
+        in.converged = m.state->converged;
+        in.error = m.state->error;
+        in.error_src = m.state->error_src;
+        in.last_L = m.state->last_L;
+        in.last_diff = m.state->last_diff;
+    }
+    for (int c = 1; c < m.nsrc; ++c) {
+        double x[SB];
+#pragma unroll
+        for (int q = 0; q < SB; ++q) {
+            const long long idx = (long long)q * BLK + tid;
+            x[q] = m.src[c * len + (idx < len ? idx : len - 1)];
+        }
+#pragma unroll
+        for (int q = 0; q < SB; ++q) v[q] += x[q];
+    }
+    PHASE_DRAIN(9);
+    // ---- L = LSE_r log P_r (:503) in two passes: max, then sum of exp(m - max) ----
+    double mx = -INFINITY;
+#pragma unroll
+    for (int q = 0; q < PB; ++q) {
+        const bool ok = (long long)q * BLK + tid < nb && ps[q] > 0.0;
+        mx = ok ? fmax(mx, pm[q]) : mx;
+    }
+    for (long long r = (long long)PB * BLK + tid; r < nb; r += BLK)  // > 512 workgroups
+        if (m.llpart[2 * r + 1] > 0.0) mx = fmax(mx, m.llpart[2 * r]);
+    mx = wave_max(mx);
+    if (lane == 0) sMx[wv] = mx;
+#pragma unroll
+    for (int q = 0; q < SB; ++q) {
+        const int idx = q * BLK + tid;
+        if (idx < NSM) sSm[idx] = (idx < len) ? v[q] : 0.0;
+    }
+    if (tid == 0) {
+        sIn = in;
+        // multi-rank: the same fixed-order fold as the standalone M-step kernels of other ranks
+        if (!m.local_lse) sLr = lse_rank_pairs(m.llpart, nb);
+    }
+    __syncthreads();
+    PHASE(6);
+    if (sIn.done) {  // converged before this launch: device-side no-op
+        if (tid == 0 && bid == 0) *m.state_out = sIn;
+        return false;
+    }
+    double Mb = sMx[0];
+#pragma unroll
+    for (int w = 1; w < NW; ++w) Mb = fmax(Mb, sMx[w]);
+    double sum = 0.0;
+    if (Mb != -INFINITY) {
+#pragma unroll
+        for (int q = 0; q < PB; ++q) {
+            const bool ok = (long long)q * BLK + tid < nb && ps[q] > 0.0;
+            sum += ok ? ps[q] * exp(pm[q] - Mb) : 0.0;
+        }
+        for (long long r = (long long)PB * BLK + tid; r < nb; r += BLK)
+            if (m.llpart[2 * r + 1] > 0.0) sum += m.llpart[2 * r + 1] * exp(m.llpart[2 * r] - Mb);
+    }
+    sum = gsum<64>(sum);
+    if (lane == 0) sSum[wv] = sum;
+    PHASE(7);
+    // pi (:415-424), A (:429-455) into LDS, by the stand-alone variants' formulas (mstep.hpp)
+    if (tid < G) sPA[tid] = tid < N ? mstep_pi(sSm[tid], m.R_global) : 0.0;
+    if (tid < N * N) {
+        const double den = sSm[N + N * N + tid / N];
+        const double num = sSm[N + tid];
+        sPA[G + tid] = mstep_a(num, den);
+    }
+    // B (:460-497) from the registers straight into the emission table (and HBM, workgroup 0).
+    // Element e = q * BLK + tid - NSM is symbol e / N, state e % N; with N | BLK the state (and
+    // so the denominator) is the same for every q of a thread: one reciprocal per thread.
+    const bool w0 = bid == 0;
+    const int e0 = tid - NSM;
+    constexpr bool kSameState = (BLK % N) == 0;
+    const int jj0 = ((e0 % N) + N) % N;
+    const double inv0 = kSameState ? mstep_inv(sSm[N + N * N + N + jj0]) : 0.0;
+    // PT: a_jj and a_{j-1,j} of the element's state, the same arithmetic as sPA's A (:429-455)
+    auto a_of = [&](int r, int c) -> double {
+        const double den = sSm[N + N * N + r];
+        const double num = sSm[N + r * N + c];
+        return mstep_a(num, den);
+    };
+    double ad0 = 0.0, ai0 = 0.0;
+    if constexpr (PT && kSameState) {
+        ad0 = a_of(jj0, jj0);
+        ai0 = jj0 >= 1 ? a_of(jj0 - 1, jj0) : 0.0;
+    }
+    double bval[SB];
+#pragma unroll
+    for (int q = 0; q < SB; ++q) {
+        const int e = q * BLK + e0;
+        const int jj = kSameState ? jj0 : ((e % N) + N) % N;
+        const double inv = kSameState ? inv0 : mstep_inv(sSm[N + N * N + N + jj]);
+        bval[q] = bnum_to_b(v[q], inv);
+        if (e >= 0 && e < K * N) {
+            const int i = (e / N) * GP + jj;
+            if constexpr (PT) {
+                const double ad = kSameState ? ad0 : a_of(jj, jj);
+                const double ai = kSameState ? ai0 : (jj >= 1 ? a_of(jj - 1, jj) : 0.0);
+                tab_put<PT, GP, LAY>(sP, sH, i, ad * bval[q], ai * bval[q], bval[q]);  // histogram zeroed, b
+            } else {
+                tab_put<PT, GP, LAY>(sP, sH, i, 0.0, 0.0, bval[q]);
+            }
+        }
+    }
+    if (w0) {
+#pragma unroll
+        for (int q = 0; q < SB; ++q) {
+            const int e = q * BLK + e0;
+            if (e >= 0 && e < K * N) {
+                const int k = e / N, jj = e - k * N;
+                m.B[(long long)jj * K + k] = bval[q];  // put_b without its column order: N <= 16 here
+                m.Bt[(long long)k * G + jj] = bval[q];
+            }
+        }
+    }
+    PHASE(10);
+    // zero the pad columns [N, GP) of every row (products, histogram, b)
+    if constexpr (GP > N) {
+        for (int i = tid; i < K * (GP - N); i += BLK) {
+            const int k = i / (GP - N), c = N + (i - k * (GP - N));
+            tab_put<PT, GP, LAY>(sP, sH, k * GP + c, 0.0, 0.0, 0.0);
+        }
+    }
+    __syncthreads();
+    double S = 0.0;
+#pragma unroll
+    for (int w = 0; w < NW; ++w) S += sSum[w];
+    const double L = m.local_lse ? ((S > 0.0) ? Mb + log(S) : -INFINITY) : sLr;
+    const double diff = (sIn.prev_L != -INFINITY) ? fabs(L - sIn.prev_L) : INFINITY;  // :505-508
+    const bool cont = (diff >= sIn.epsilon) && (sIn.iteration + 1 < sIn.max_iterations);  // :346
+    if (w0) {
+        if (tid < N) m.pi[tid] = sPA[tid];
+        if (tid < N * N) m.A[tid] = sPA[G + tid];
+        if (tid == 0) record_iteration(m, sIn, L);
+    }
+    return cont;
+}
 
 // Body of the small-N E-step / scorer for workgroup `bid` of the `nblk` workgroups that cover one
 // model's sequences: the whole grid of k_estep_small, or one model's slice of a grouped launch
@@ -555,12 +295,12 @@ __device__ __forceinline__ void estep_small_body(const EArgs &a, const long long
     static_assert(!DET || (LDSTAB && !FWD_ONLY), "deterministic mode: E-step with LDS tables");
     constexpr bool JOIN = BLK > kBlock;
     static_assert(!JOIN || (BLK == 2 * kBlock && LDSTAB && !FWD_ONLY && !DET), "joined map: E-step with LDS tables");
-    static_assert(LAY == 0 || (LAY == 1 && JOIN && G == 8 && kTabPad == 0), "class-split tables: joined map, G = 8");
+    static_assert(LAY == 0 || (LAY == 1 && JOIN && G == 8), "class-split tables: joined map, G = 8");
     // H entry - P entry of a lane's step address: the immediate offset of the histogram add and the H.b read
     constexpr int HOFF = LAY ? lay2_hist_off(G) : kHistOff;
     constexpr int U = kWave / G;
     // dense G = 8: xi on the 4x4x4 MFMA (xi_mfma8), two accumulators per lane in its D layout
-    constexpr bool XM = !LR && G == 8 && !FWD_ONLY && HMMBW_XI_MFMA;
+    constexpr bool XM = !LR && G == 8 && !FWD_ONLY;
     constexpr int NSR = LR ? 2 : N;     // S columns per state in the block reduction (row j of S)
     constexpr int NS = XM ? 2 : NSR;    // per-lane S accumulators
     constexpr int NV = NSR + 3;         // + gamma_den_excl, gamma_den_all, pi_num
@@ -568,8 +308,8 @@ __device__ __forceinline__ void estep_small_body(const EArgs &a, const long long
     // layout; the host sizes it), so the backward loads z instead of recomputing it: the recompute is
     // 16 of the dense step's ~70 VALU instructions; the 128 MB at cfg3 go through HBM (275 MB of
     // traffic per launch, 0.46 of the HBM peak over the kernel: not the bound, profiles/r3)
-    constexpr bool ZF = !LR && !FWD_ONLY && HMMBW_ZFULL;
-    constexpr int GP = LDSTAB ? G + kTabPad : G;  // row stride of the emission / histogram tables
+    constexpr bool ZF = !LR && !FWD_ONLY;
+    constexpr int GP = G;  // row stride of the emission / histogram tables
     // left-to-right with LDS tables: per (symbol, state) products {a_jj b_j(o), a_{j-1,j} b_j(o)}
     constexpr bool PT = LR && LDSTAB;
     // split extra waves possible in this instantiation: dense E-step with LDS tables and atomic statistics
@@ -578,7 +318,7 @@ __device__ __forceinline__ void estep_small_body(const EArgs &a, const long long
     // registers, profiles/r5/split_extra_ab.txt)
     // (joined map: the split groups hand over through an LDS flag instead of a workgroup barrier, which would
     // also hold the full workgroup's waves)
-    constexpr bool SPLITOK = (!LR || (HMMBW_SPLIT_LR && JOIN)) && LDSTAB && !FWD_ONLY && !DET;
+    constexpr bool SPLITOK = (!LR || JOIN) && LDSTAB && !FWD_ONLY && !DET;
     extern __shared__ __attribute__((aligned(256))) double smem[];  // 256-B aligned whatever the static LDS (ds_read_b128 rows)
     __shared__ double sPA[G + N * N];  // pi (zero-padded to G) and A of this iteration
     const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
@@ -668,13 +408,8 @@ __device__ __forceinline__ void estep_small_body(const EArgs &a, const long long
 
     if (wactive && wave < a.L.nwaves) {
         const long long slot = wave * U + u;
-#ifdef HMMBW_DIAG_XHALF  // diagnostics (timing only, results wrong): the spread map's extra waves run half their steps
-        const int Tw = xblk ? max(kChunk, (a.L.wave_T[wave] / 2) & ~(kChunk - 1)) : a.L.wave_T[wave];
-        const int T = min(a.L.slot_len[slot], Tw);
-#else
         const int T = a.L.slot_len[slot];
         const int Tw = a.L.wave_T[wave];
-#endif
         const int seq = a.L.slot_seq[slot];
         const bool full = a.L.wave_full[wave] != 0;
         const int nch = (Tw + kChunk - 1) / kChunk;
@@ -888,9 +623,8 @@ __device__ __forceinline__ void estep_small_body(const EArgs &a, const long long
                     if (SPLITOK && k == 0) Ch = (c == hc) ? C : Ch;  // split: C_h, h = 8 hc
                     sp[k] = st;
                     if constexpr (!FWD_ONLY) {
-                        if (ZF) {  // every z_t
-                            if constexpr (HMMBW_ZF_NT) __builtin_nontemporal_store(z, &ckw[((long long)c * kChunk + k) * kWave]);
-                            else ckw[((long long)c * kChunk + k) * kWave] = z;
+                        if (ZF) {  // every z_t (nontemporal measured worse, cfg3 dense 79.7-80.5 against 73.6-73.8 us)
+                            ckw[((long long)c * kChunk + k) * kWave] = z;
                         } else if (k == 0) {
                             ckw[(long long)c * kWave] = z;  // checkpoint z_{8c}
                         }
@@ -1052,10 +786,7 @@ __device__ __forceinline__ void estep_small_body(const EArgs &a, const long long
                 auto ldz = [&](double (&zz)[ZF ? kChunk : 1], int c) {
                     if constexpr (ZF) {
 #pragma unroll
-                        for (int k = 0; k < kChunk; ++k) {
-                            if constexpr (HMMBW_ZF_NT) zz[k] = __builtin_nontemporal_load(&ckw[((long long)c * kChunk + k) * kWave]);
-                            else zz[k] = ckw[((long long)c * kChunk + k) * kWave];
-                        }
+                        for (int k = 0; k < kChunk; ++k) zz[k] = ckw[((long long)c * kChunk + k) * kWave];
                     }
                 };
                 Ld X[4];
@@ -1213,7 +944,6 @@ __device__ __forceinline__ void estep_small_body(const EArgs &a, const long long
                     // next chunk's emission rows go to LDS before this chunk's histogram atomics, so
                     // they are not queued behind them
                     ldrows(bvn, bun, han, pkn);
-#ifndef HMMBW_NO_HIST  // diagnostics build: no B-numerator histogram
                     if constexpr (DET) {
                         // gamma row of every position (position = index of the symbol in the pack layout)
                         double *gr = a.gam + (symbase + (long long)c * U * kChunk) * G + j;
@@ -1230,7 +960,6 @@ __device__ __forceinline__ void estep_small_body(const EArgs &a, const long long
                         for (int k = 0; k < kChunk; ++k)
                             if (gk[k] != 0.0) unsafeAtomicAdd(&accb[a.off_bnum + (long long)sym_of(pkA, k) * N + j], gk[k]);
                     }
-#endif
                     if constexpr (!PT) {
                         f_hi = fs[0];
                         if constexpr (LR) fu_hi = fus[0];
@@ -1329,13 +1058,11 @@ __device__ __forceinline__ void estep_small_body(const EArgs &a, const long long
     }
 
     __syncthreads();
-#if HMMBW_FLUSH_VMWAIT
     // every load of the sweeps has landed long ago; saying so here keeps the compiler from waiting on the
     // flush's global atomics below: at the join of the active and idle waves' paths it otherwise counts a
     // ring load as possibly in flight and, before reusing its register, waits vmcnt(2), i.e. for the
     // round trips of all but two of the histogram atomics issued after it
     __builtin_amdgcn_s_waitcnt(0x0F70);  // vmcnt(0)
-#endif
     // the B-numerator histogram's atomics first: their round trips overlap the reductions below
     if constexpr (!FWD_ONLY && !DET && LDSTAB) if (!(a.ablate & 1)) {
         // (round 4: starting each workgroup's pass at a different row, so that workgroups finishing together
@@ -1387,7 +1114,7 @@ __device__ __forceinline__ void estep_small_body(const EArgs &a, const long long
             const bool ok = sw > 0.0;
             const double M = wave_max(ok ? mw : -INFINITY);
             const double S = gsum<64>((ok && M != -INFINITY) ? sw * exp(mw - M) : 0.0);
-            // memory-side atomics: the fused M-step of the last workgroup reads these with atomics too
+            // memory-side atomics: in a fused multi-rank launch rank_ll_fold reads the pairs with atomics too
             if (lane == 0) {
                 atomicExch(&a.llpart[2 * bid], (S > 0.0) ? M : 0.0);
                 atomicExch(&a.llpart[2 * bid + 1], S);
@@ -1473,9 +1200,7 @@ __device__ __forceinline__ void estep_small_body(const EArgs &a, const long long
 
 template <int N, int G, bool LR, bool LDSTAB, bool FWD_ONLY, bool DET = false>
 __global__ void __launch_bounds__(kBlock, 2) k_estep_small(EArgs a) {  // 2 waves per SIMD (<= 256 VGPRs)
-#if HMMBW_KARG_TOUCH
     touch_kernargs<EArgs>();
-#endif
     estep_small_body<N, G, LR, LDSTAB, FWD_ONLY, DET>(a, blockIdx.x, gridDim.x);
 }
 
@@ -1484,9 +1209,7 @@ __global__ void __launch_bounds__(kBlock, 2) k_estep_small(EArgs a) {  // 2 wave
 // their split B partners (hand-over by LDS flag).
 template <int N, int G, bool LR, int LAY = 0>
 __global__ void __launch_bounds__(2 * kBlock, 1) k_estep_join(EArgs a) {
-#if HMMBW_KARG_TOUCH
     touch_kernargs<EArgs>();
-#endif
     estep_small_body<N, G, LR, true, false, false, 2 * kBlock, LAY>(a, blockIdx.x, gridDim.x);
 }
 
@@ -1505,572 +1228,6 @@ __global__ void __launch_bounds__(kBlock, 2) k_estep_small_group(GroupArgs g) {
     }
     const long long b0 = g.start[lo];
     estep_small_body<N, G, LR, LDSTAB, FWD_ONLY>(g.args[lo], b - b0, g.start[lo + 1] - b0);
-}
-
-// ---------------------------------------------------------------------------------------------
-// Block reductions
-// ---------------------------------------------------------------------------------------------
-__device__ double block_reduce(double x, double *sh, bool is_max) {
-    const int tid = threadIdx.x;
-    x = is_max ? wave_max(x) : gsum<64>(x);
-    __syncthreads();
-    if ((tid & 63) == 0) sh[tid >> 6] = x;
-    __syncthreads();
-    if (tid < 64) {
-        const int nw = blockDim.x >> 6;
-        double y = tid < nw ? sh[tid] : (is_max ? -INFINITY : 0.0);
-        y = is_max ? wave_max(y) : gsum<64>(y);
-        if (tid == 0) sh[0] = y;
-    }
-    __syncthreads();
-    const double r = sh[0];
-    __syncthreads();
-    return r;
-}
-
-// Combine per-block (max, sum exp) pairs into this rank's pair (log_sum_exp :66-79 over :503).
-// ATOMIC: read with returning memory-side atomics (inside the producing kernel, where the per-XCD
-// L2s give no cross-workgroup visibility for plain loads).
-template <bool ATOMIC = false>
-__device__ __forceinline__ double rd(const double *p) {
-    if constexpr (ATOMIC) return unsafeAtomicAdd(const_cast<double *>(p), 0.0);
-    else return *p;
-}
-
-template <bool ATOMIC = false>
-__device__ void combine_ll_pairs(const double *pairs, long long n, double *sh, double *m_out, double *s_out) {
-    double mx = -INFINITY;
-    for (long long r = threadIdx.x; r < n; r += blockDim.x)
-        if (rd<ATOMIC>(&pairs[2 * r + 1]) > 0.0) mx = fmax(mx, rd<ATOMIC>(&pairs[2 * r]));
-    mx = block_reduce(mx, sh, true);
-    double s = 0.0;
-    if (mx != -INFINITY)
-        for (long long r = threadIdx.x; r < n; r += blockDim.x) {
-            const double sr = rd<ATOMIC>(&pairs[2 * r + 1]);
-            if (sr > 0.0) s += sr * exp(rd<ATOMIC>(&pairs[2 * r]) - mx);
-        }
-    s = block_reduce(s, sh, false);
-    *m_out = mx;
-    *s_out = s;
-}
-
-
-
-// sum of one statistic over the copies, clearing them for the next iteration
-template <bool ATOMIC>
-__device__ __forceinline__ double take(const MArgs &m, long long idx) {
-    double v = 0.0;
-    double *p = const_cast<double *>(m.src) + idx;
-    for (int c = 0; c < m.nsrc; ++c) {
-        if constexpr (ATOMIC) {
-            v += atomicExch(p + c * m.copy_len, 0.0);
-        } else {
-            v += p[c * m.copy_len];
-            p[c * m.copy_len] = 0.0;
-        }
-    }
-    return v;
-}
-
-// B entry from its numerator and the reciprocal of its row's denominator (:460-497): 1e-20 floor when
-// no gamma term carries the symbol, 0 for an empty row.  Shared by every M-step variant, so they
-// produce bit-identical parameters.
-// Column of state j in the wide kernels' emission table (estep_mfma.hpp): j = 16m + 4r + g is stored
-// at 16m + 4g + r, so the 4 states one lane owns are contiguous.
-__host__ __device__ inline int bt_col(int j) { return (j & ~15) | ((j & 3) << 2) | ((j >> 2) & 3); }
-
-__device__ __forceinline__ double mstep_inv(double den) { return den > 0.0 ? 1.0 / den : 0.0; }
-__device__ __forceinline__ double bnum_to_b(double num, double inv) {
-    return inv > 0.0 ? (num > 0.0 ? num * inv : 1e-20) : 0.0;
-}
-
-// Convergence record of one EM iteration (hmm_training.py:503-514): L of the parameters that entered
-// it, diff (+inf on the first iteration), the stop rule of :346; written to the next state slot.
-__device__ bool record_iteration(const MArgs &m, const IterState &in, double L) {
-    const double diff = (in.prev_L != -INFINITY) ? fabs(L - in.prev_L) : INFINITY;  // :505-508
-    const long long it = in.iteration;
-    const bool cont = (diff >= in.epsilon) && (it + 1 < in.max_iterations);
-    m.hist[2 * (it % kHist)] = L;
-    m.hist[2 * (it % kHist) + 1] = diff;
-    IterState o = in;
-    o.prev_L = L;
-    o.last_L = L;
-    o.last_diff = diff;
-    o.iteration = it + 1;
-    if (!cont) {
-        o.done = 1;
-        o.converged = (it + 1 < in.max_iterations) ? 1 : 0;
-    }
-    *m.state_out = o;
-    if (m.live != nullptr) {  // the host mirror: record and state first, then (acknowledged) the publication
-        auto sys = [](auto *p, auto v) { __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM); };
-        sys(&m.live->hist[2 * (it % kHist)], L);
-        sys(&m.live->hist[2 * (it % kHist) + 1], diff);
-        IterState *sl = &m.live->slot[o.iteration & 1];
-        sys(&sl->prev_L, o.prev_L);
-        sys(&sl->last_L, o.last_L);
-        sys(&sl->last_diff, o.last_diff);
-        sys(&sl->epsilon, o.epsilon);
-        sys(&sl->iteration, o.iteration);
-        sys(&sl->max_iterations, o.max_iterations);
-        sys(&sl->done, o.done);
-        sys(&sl->converged, o.converged);
-        sys(&sl->error, o.error);
-        sys(&sl->error_src, o.error_src);
-        __builtin_amdgcn_s_waitcnt(0x0F70);  // vmcnt(0): every store above is acknowledged
-        sys(&m.live->pub, ((unsigned long long)m.live_epoch << 32) | (unsigned long long)(unsigned)o.iteration);
-    }
-    return cont;
-}
-
-// L = LSE_r log P_r (:503) from one all-reduced (max, sum exp) pair per rank, by ONE thread in rank
-// order.  Every multi-rank M-step variant (the merged prologue, k_mstep, k_mstep_grid) forms L with
-// this function, so ranks that run different variants (an empty shard cannot merge its M-step) still
-// hold bitwise-identical L and diff and take the same stop decision (:346).
-__device__ __forceinline__ double lse_rank_pairs(const double *ll, long long n) {
-    double mx = -INFINITY;
-    for (long long r = 0; r < n; ++r)
-        if (ll[2 * r + 1] > 0.0) mx = fmax(mx, ll[2 * r]);
-    double s = 0.0;
-    if (mx != -INFINITY)
-        for (long long r = 0; r < n; ++r)
-            if (ll[2 * r + 1] > 0.0) s += ll[2 * r + 1] * exp(ll[2 * r] - mx);
-    return (s > 0.0) ? mx + log(s) : -INFINITY;
-}
-
-// M-step kernels entered after convergence carry the state over to the next slot and do nothing else
-__device__ __forceinline__ bool carry_if_done(const MArgs &m) {
-    if (!m.state->done) return false;
-    if (threadIdx.x == 0 && blockIdx.x == 0) *m.state_out = *m.state;
-    return true;
-}
-
-// M-step + convergence by one workgroup of 256 threads (hmm_training.py:415-514).
-template <bool ATOMIC>
-__device__ void mstep_block(const MArgs &m) {
-    __shared__ double sh[16];
-    __shared__ double sL;
-    __shared__ double sPi[64], sGex[64], sGall[64];
-    const IterState *st = m.state;
-    const int tid = threadIdx.x;
-    // L = LSE_r log P_r over all ranks (:503)
-    if (m.local_lse) {
-        double mx, s;
-        combine_ll_pairs<ATOMIC>(m.llpart, m.nblocks, sh, &mx, &s);
-        if (tid == 0) sL = (s > 0.0) ? mx + log(s) : -INFINITY;
-    } else if (tid == 0) {
-        sL = lse_rank_pairs(m.llpart, m.nblocks);  // one (max, sum exp) pair per rank, all-reduced
-        for (long long r = 0; r < 2 * m.nblocks; ++r) m.zero_ll[r] = 0.0;
-    }
-    const int N = m.N, K = m.K;
-    for (int i = tid; i < N; i += blockDim.x) {
-        sPi[i] = take<ATOMIC>(m, i);
-        sGex[i] = take<ATOMIC>(m, m.off_gex + i);
-        sGall[i] = take<ATOMIC>(m, m.off_gall + i);
-    }
-    __syncthreads();
-    // pi (:415-424): LSE_r gamma_0 - log R ; no term -> -inf
-    for (int i = tid; i < N; i += blockDim.x) m.pi[i] = sPi[i] > 0.0 ? sPi[i] / (double)m.R_global : 0.0;
-    // A (:429-455): xi numerator; denominator excludes the last frame
-    for (int idx = tid; idx < N * N; idx += blockDim.x) {
-        const double den = sGex[idx / N];
-        const double num = take<ATOMIC>(m, m.off_S + idx);
-        m.A[idx] = (den > 0.0 && num > 0.0) ? num / den : 0.0;
-    }
-    // B (:460-497): floor 1e-20 when no gamma term carries the symbol; empty denominator -> row 0
-    for (long long idx = tid; idx < (long long)N * K; idx += blockDim.x) {
-        const int jj = (int)(idx % N), k = (int)(idx / N);  // symbol-major: coalesced over the copies
-        const double num = take<ATOMIC>(m, m.off_bnum + idx);
-        const double v = bnum_to_b(num, mstep_inv(sGall[jj]));
-        m.B[(long long)jj * K + k] = v;
-        m.Bt[(long long)k * m.G + (m.bt_perm ? bt_col(jj) : jj)] = v;
-    }
-    __syncthreads();
-    if (tid == 0) record_iteration(m, *st, sL);
-}
-
-
-
-// M-step + convergence spread over the whole grid (large N x K, e.g. the wide path's 64 x 1024 B):
-// every workgroup re-estimates its grid-stride share of B (:460-497) and A (:429-455) from the
-// statistics summed over the copies; workgroup 0 also does pi (:415-424), L and the convergence
-// record (:503-514).  The statistics are only read (each E-step launch clears the buffer it will fill), so
-// no workgroup depends on another.
-__device__ __forceinline__ double peek(const MArgs &m, long long idx) {
-    double v = 0.0;
-    for (int c = 0; c < m.nsrc; ++c) v += m.src[c * m.copy_len + idx];
-    return v;
-}
-
-__device__ void mstep_grid(const MArgs &m) {
-    __shared__ double sh[16];
-    __shared__ double sL;
-    __shared__ double sGall[64];
-    const int tid = threadIdx.x;
-    const int N = m.N, K = m.K;
-    for (int i = tid; i < N; i += blockDim.x) sGall[i] = mstep_inv(peek(m, m.off_gall + i));
-    __syncthreads();
-    for (long long idx = (long long)blockIdx.x * blockDim.x + tid; idx < (long long)N * K;
-         idx += (long long)gridDim.x * blockDim.x) {
-        const int jj = (int)(idx % N), k = (int)(idx / N);  // symbol-major: coalesced reads
-        const double v = bnum_to_b(peek(m, m.off_bnum + idx), sGall[jj]);
-        m.B[(long long)jj * K + k] = v;
-        m.Bt[(long long)k * m.G + (m.bt_perm ? bt_col(jj) : jj)] = v;
-    }
-    for (long long idx = (long long)blockIdx.x * blockDim.x + tid; idx < (long long)N * N;
-         idx += (long long)gridDim.x * blockDim.x) {  // A (:429-455)
-        const double den = peek(m, m.off_gex + idx / N);
-        const double num = peek(m, m.off_S + idx);
-        m.A[idx] = (den > 0.0 && num > 0.0) ? num / den : 0.0;
-    }
-    if (blockIdx.x != 0) return;
-    if (m.local_lse) {
-        double mx, s;
-        combine_ll_pairs<false>(m.llpart, m.nblocks, sh, &mx, &s);
-        if (tid == 0) sL = (s > 0.0) ? mx + log(s) : -INFINITY;
-    } else if (tid == 0) {
-        sL = lse_rank_pairs(m.llpart, m.nblocks);  // one (max, sum exp) pair per rank, all-reduced
-    }
-    for (int i = tid; i < N; i += blockDim.x) {
-        const double pn = peek(m, i);
-        m.pi[i] = pn > 0.0 ? pn / (double)m.R_global : 0.0;
-    }
-    __syncthreads();
-    if (tid == 0) record_iteration(m, *m.state, sL);
-}
-
-// merge (max, sum exp) pairs: online log-sum-exp
-__device__ __forceinline__ void ll_merge(double &M, double &S, double m2, double s2) {
-    if (!(s2 > 0.0)) return;
-    if (!(S > 0.0)) { M = m2; S = s2; return; }
-    if (m2 > M) { S = S * exp(M - m2) + s2; M = m2; }
-    else S += s2 * exp(m2 - M);
-}
-
-// M-step staged through LDS (sSt: copy_len doubles): the statistics (summed over the copies, which
-// are cleared) and the per-workgroup log-likelihood pairs are gathered in independent batches, then
-// the update runs from LDS.  ATOMIC (fused into the E-step): gathered with returning memory-side
-// atomics; otherwise (its own kernel, after a kernel boundary) with plain loads.
-template <bool ATOMIC>
-__device__ void mstep_staged(const MArgs &m, double *sSt) {
-    __shared__ double sM[16], sS[16];
-    __shared__ double sL;
-    const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6, nw = blockDim.x >> 6;
-    const int N = m.N, K = m.K;
-    const long long len = m.copy_len;
-    // ---- one batch of independent loads: convergence state, LL pairs, statistics ----
-    IterState in{};
-    if (tid == 0) in = *m.state;
-    // Branch-free, clamped addresses so the compiler issues every load of a batch before the first
-    // wait (a guarded load inside a runtime loop serialises on its own s_waitcnt).
-    constexpr int PB = 4;
-    double pm[PB], ps[PB];
-    double M = -INFINITY, S = 0.0;
-    const long long nb = m.nblocks;  // >= 1 (a launch with no workgroups leaves nothing pending)
-    for (long long r0 = 0; r0 < nb; r0 += (long long)PB * blockDim.x) {
-#pragma unroll
-        for (int u = 0; u < PB; ++u) {
-            const long long r = r0 + (long long)u * blockDim.x + tid;
-            const long long rc = r < nb ? r : nb - 1;
-            pm[u] = rd<ATOMIC>(m.llpart + 2 * rc);
-            ps[u] = rd<ATOMIC>(m.llpart + 2 * rc + 1);
-        }
-#pragma unroll
-        for (int u = 0; u < PB; ++u) {
-            const bool ok = r0 + (long long)u * blockDim.x + tid < nb;
-            ll_merge(M, S, ok ? pm[u] : -INFINITY, ok ? ps[u] : 0.0);
-        }
-    }
-    constexpr int B = 16;
-    double *src = const_cast<double *>(m.src);
-    for (long long base = 0; base < len; base += (long long)B * blockDim.x) {
-        double v[B];
-#pragma unroll
-        for (int u = 0; u < B; ++u) v[u] = 0.0;
-        for (int c = 0; c < m.nsrc; ++c) {
-            double x[B];
-#pragma unroll
-            for (int u = 0; u < B; ++u) {
-                const long long idx = base + (long long)u * blockDim.x + tid;
-                double *q = src + c * len + (idx < len ? idx : len - 1);
-                if constexpr (ATOMIC) x[u] = idx < len ? atomicExch(q, 0.0) : 0.0;
-                else x[u] = *q;
-            }
-#pragma unroll
-            for (int u = 0; u < B; ++u) v[u] += x[u];
-        }
-#pragma unroll
-        for (int u = 0; u < B; ++u) {
-            const long long idx = base + (long long)u * blockDim.x + tid;
-            if (idx < len) {
-                sSt[idx] = v[u];
-                if constexpr (!ATOMIC)
-                    for (int c = 0; c < m.nsrc; ++c) src[c * len + idx] = 0.0;
-            }
-        }
-    }
-    // ---- L = LSE_r log P_r (:503) ----
-    for (int k = 32; k >= 1; k >>= 1) ll_merge(M, S, __shfl_xor(M, k), __shfl_xor(S, k));
-    if (lane == 0) { sM[wv] = M; sS[wv] = S; }
-    __syncthreads();
-    if (tid == 0) {
-        double MM = -INFINITY, SS = 0.0;
-        for (int w = 0; w < nw; ++w) ll_merge(MM, SS, sM[w], sS[w]);
-        sL = (SS > 0.0) ? MM + log(SS) : -INFINITY;
-    }
-    __syncthreads();
-    const double *sPi = sSt, *sS_ = sSt + m.off_S, *sGex = sSt + m.off_gex, *sGall = sSt + m.off_gall,
-                 *sBn = sSt + m.off_bnum;
-    // pi (:415-424), A (:429-455), B (:460-497)
-    if (tid < N) m.pi[tid] = sPi[tid] > 0.0 ? sPi[tid] / (double)m.R_global : 0.0;
-    if (tid < N * N) {
-        const double den = sGex[tid / N];
-        const double num = sS_[tid];
-        m.A[tid] = (den > 0.0 && num > 0.0) ? num / den : 0.0;
-    }
-    for (int idx = tid; idx < N * K; idx += blockDim.x) {
-        const int k = idx / N, jj = idx - k * N;
-        const double v = bnum_to_b(sBn[idx], mstep_inv(sGall[jj]));
-        m.B[(long long)jj * K + k] = v;
-        m.Bt[(long long)k * m.G + (m.bt_perm ? bt_col(jj) : jj)] = v;
-    }
-    if (tid == 0) record_iteration(m, in, sL);
-}
-
-// The previous iteration's M-step + convergence step (hmm_training.py:415-514), run by EVERY
-// workgroup of the merged E-step launch, straight into its LDS tables: every workgroup reads the same
-// statistics and log-likelihood pairs and applies the same arithmetic in the same order, so all of
-// them hold bit-identical parameters and reach the same stop decision.  Workgroup 0 also writes the
-// parameters back to HBM (for the queries) and records the iteration in the other state slot.
-// Returns false when EM stops here (or had stopped before).
-constexpr int kMergedMaxStats = 16 * kBlock;  // statistics per launch the prologue holds in registers
-
-__device__ __forceinline__ double wave_max(double x) {
-    x = fmax(x, dpp<0xB1>(x));
-    x = fmax(x, dpp<0x4E>(x));
-    x = fmax(x, dpp<0x141>(x));
-    x = fmax(x, dpp<0x140>(x));
-    x = max_swap<false>(x);
-    return max_swap<true>(x);
-}
-
-// Multi-rank fused E-step (hmmbw_iterate with the engine communicator): the workgroups accumulate
-// straight into the all-reduce buffer, and wave 0 of the LAST workgroup to count its pair in (completion
-// counter) folds the per-workgroup (max, sum exp) pairs into this rank's slot (what k_reduce_local did
-// in its own launch).  No __threadfence: a device-scope release writes back the XCD's L2 (this launch's
-// checkpoints), which cost ~20 us per launch; the pairs are memory-side atomics, so thread 0 only has
-// to see its own pair land (vmcnt(0)) before it counts, and the folding wave reads them with atomics.
-__device__ __forceinline__ int rank_ll_count(const EArgs &a) {
-    __builtin_amdgcn_s_waitcnt(0x0F70);  // s_waitcnt vmcnt(0): block_ll_partial's atomicExch has landed
-    return atomicAdd(a.done_ctr, 1);
-}
-
-__device__ __forceinline__ void rank_ll_fold(const EArgs &a, long long nblk) {  // one wave
-    const int lane = threadIdx.x & 63;
-    double tm = -INFINITY, ts = 0.0;
-    for (long long r0 = 0; r0 < nblk; r0 += 4 * 64) {
-        double pm[4], ps[4];  // every round's memory-side reads issued together
-#pragma unroll
-        for (int q = 0; q < 4; ++q) {
-            const long long r = r0 + lane + q * 64;
-            pm[q] = r < nblk ? rd<true>(&a.llpart[2 * r]) : 0.0;
-            ps[q] = r < nblk ? rd<true>(&a.llpart[2 * r + 1]) : 0.0;
-        }
-#pragma unroll
-        for (int q = 0; q < 4; ++q) {
-            if (!(ps[q] > 0.0)) continue;
-            if (pm[q] > tm) {
-                ts = (tm == -INFINITY) ? ps[q] : ps[q] + ts * exp(tm - pm[q]);
-                tm = pm[q];
-            } else {
-                ts += ps[q] * exp(pm[q] - tm);
-            }
-        }
-    }
-    const double mx = wave_max(tm);
-    const double s = gsum<64>((mx != -INFINITY && ts > 0.0) ? ts * exp(tm - mx) : 0.0);
-    if (lane == 0) {
-        atomicExch(&a.rank_ll[0], (s > 0.0) ? mx : 0.0);
-        atomicExch(&a.rank_ll[1], s);
-        atomicExch(a.done_ctr, 0);
-    }
-}
-
-template <int N, int G, int GP, bool PT, int BLK, int LAY>
-__device__ __forceinline__ bool merged_mstep(const EArgs &a, double *sP, double *sH, double *sPA, long long bid) {
-    constexpr int NSM = N + N * N + 2 * N;  // pi_num, xi, gamma_den_excl, gamma_den_all
-    constexpr int NW = BLK / 64;
-    constexpr int SB = kMergedMaxStats / BLK;
-    constexpr int PB = 2;                   // log-likelihood pairs per thread per pass
-    __shared__ double sSm[NSM];
-    __shared__ double sMx[NW], sSum[NW];
-    __shared__ double sLr;  // multi-rank: L from the per-rank pairs (lse_rank_pairs)
-    __shared__ IterState sIn;
-    const MArgs &m = a.m;
-    const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
-    const int K = a.K;
-    const long long len = m.copy_len;
-    PHASE(8);
-    // ---- every load issued before any use: statistics, log-likelihood pairs, convergence state (the
-    // pairs and the state before the other copies' statistics are waited for: one latency, not two) ----
-    double v[SB];
-#pragma unroll
-    for (int q = 0; q < SB; ++q) {
-        const long long idx = (long long)q * BLK + tid;
-        v[q] = m.src[idx < len ? idx : len - 1];
-    }
-    const long long nb = m.nblocks;  // >= 1
-    double pm[PB], ps[PB];
-#pragma unroll
-    for (int q = 0; q < PB; ++q) {
-        const long long r = (long long)q * BLK + tid;
-        const long long rc = r < nb ? r : nb - 1;
-        pm[q] = m.llpart[2 * rc];
-        ps[q] = m.llpart[2 * rc + 1];
-    }
-    IterState in{};
-    if (tid == 0) {
-        in.prev_L = m.state->prev_L;
-        in.epsilon = m.state->epsilon;
-        in.iteration = m.state->iteration;
-        in.max_iterations = m.state->max_iterations;
-        in.done = m.state->done;
-        in.converged = m.state->converged;
-        in.error = m.state->error;
-        in.error_src = m.state->error_src;
-        in.last_L = m.state->last_L;
-        in.last_diff = m.state->last_diff;
-    }
-    for (int c = 1; c < m.nsrc; ++c) {
-        double x[SB];
-#pragma unroll
-        for (int q = 0; q < SB; ++q) {
-            const long long idx = (long long)q * BLK + tid;
-            x[q] = m.src[c * len + (idx < len ? idx : len - 1)];
-        }
-#pragma unroll
-        for (int q = 0; q < SB; ++q) v[q] += x[q];
-    }
-    PHASE_DRAIN(9);
-    // ---- L = LSE_r log P_r (:503) in two passes: max, then sum of exp(m - max) ----
-    double mx = -INFINITY;
-#pragma unroll
-    for (int q = 0; q < PB; ++q) {
-        const bool ok = (long long)q * BLK + tid < nb && ps[q] > 0.0;
-        mx = ok ? fmax(mx, pm[q]) : mx;
-    }
-    for (long long r = (long long)PB * BLK + tid; r < nb; r += BLK)  // > 512 workgroups
-        if (m.llpart[2 * r + 1] > 0.0) mx = fmax(mx, m.llpart[2 * r]);
-    mx = wave_max(mx);
-    if (lane == 0) sMx[wv] = mx;
-#pragma unroll
-    for (int q = 0; q < SB; ++q) {
-        const int idx = q * BLK + tid;
-        if (idx < NSM) sSm[idx] = (idx < len) ? v[q] : 0.0;
-    }
-    if (tid == 0) {
-        sIn = in;
-        // multi-rank: the same fixed-order fold as the standalone M-step kernels of other ranks
-        if (!m.local_lse) sLr = lse_rank_pairs(m.llpart, nb);
-    }
-    __syncthreads();
-    PHASE(6);
-    if (sIn.done) {  // converged before this launch: device-side no-op
-        if (tid == 0 && bid == 0) *m.state_out = sIn;
-        return false;
-    }
-    double Mb = sMx[0];
-#pragma unroll
-    for (int w = 1; w < NW; ++w) Mb = fmax(Mb, sMx[w]);
-    double sum = 0.0;
-    if (Mb != -INFINITY) {
-#pragma unroll
-        for (int q = 0; q < PB; ++q) {
-            const bool ok = (long long)q * BLK + tid < nb && ps[q] > 0.0;
-            sum += ok ? ps[q] * exp(pm[q] - Mb) : 0.0;
-        }
-        for (long long r = (long long)PB * BLK + tid; r < nb; r += BLK)
-            if (m.llpart[2 * r + 1] > 0.0) sum += m.llpart[2 * r + 1] * exp(m.llpart[2 * r] - Mb);
-    }
-    sum = gsum<64>(sum);
-    if (lane == 0) sSum[wv] = sum;
-    PHASE(7);
-    // pi (:415-424), A (:429-455) into LDS
-    if (tid < G) sPA[tid] = (tid < N && sSm[tid] > 0.0) ? sSm[tid] / (double)m.R_global : 0.0;
-    if (tid < N * N) {
-        const double den = sSm[N + N * N + tid / N];
-        const double num = sSm[N + tid];
-        sPA[G + tid] = (den > 0.0 && num > 0.0) ? num / den : 0.0;
-    }
-    // B (:460-497) from the registers straight into the emission table (and HBM, workgroup 0).
-    // Element e = q * BLK + tid - NSM is symbol e / N, state e % N; with N | BLK the state (and
-    // so the denominator) is the same for every q of a thread: one reciprocal per thread.
-    const bool w0 = bid == 0;
-    const int e0 = tid - NSM;
-    constexpr bool kSameState = (BLK % N) == 0;
-    const int jj0 = ((e0 % N) + N) % N;
-    const double inv0 = kSameState ? mstep_inv(sSm[N + N * N + N + jj0]) : 0.0;
-    // PT: a_jj and a_{j-1,j} of the element's state, the same arithmetic as sPA's A (:429-455)
-    auto a_of = [&](int r, int c) -> double {
-        const double den = sSm[N + N * N + r];
-        const double num = sSm[N + r * N + c];
-        return (den > 0.0 && num > 0.0) ? num / den : 0.0;
-    };
-    double ad0 = 0.0, ai0 = 0.0;
-    if constexpr (PT && kSameState) {
-        ad0 = a_of(jj0, jj0);
-        ai0 = jj0 >= 1 ? a_of(jj0 - 1, jj0) : 0.0;
-    }
-    double bval[SB];
-#pragma unroll
-    for (int q = 0; q < SB; ++q) {
-        const int e = q * BLK + e0;
-        const int jj = kSameState ? jj0 : ((e % N) + N) % N;
-        const double inv = kSameState ? inv0 : mstep_inv(sSm[N + N * N + N + jj]);
-        bval[q] = bnum_to_b(v[q], inv);
-        if (e >= 0 && e < K * N) {
-            const int i = (e / N) * GP + jj;
-            if constexpr (PT) {
-                const double ad = kSameState ? ad0 : a_of(jj, jj);
-                const double ai = kSameState ? ai0 : (jj >= 1 ? a_of(jj - 1, jj) : 0.0);
-                tab_put<PT, GP, LAY>(sP, sH, i, ad * bval[q], ai * bval[q], bval[q]);  // histogram zeroed, b
-            } else {
-                tab_put<PT, GP, LAY>(sP, sH, i, 0.0, 0.0, bval[q]);
-            }
-        }
-    }
-    if (w0) {
-#pragma unroll
-        for (int q = 0; q < SB; ++q) {
-            const int e = q * BLK + e0;
-            if (e >= 0 && e < K * N) {
-                const int k = e / N, jj = e - k * N;
-                m.B[(long long)jj * K + k] = bval[q];
-                m.Bt[(long long)k * G + jj] = bval[q];
-            }
-        }
-    }
-    PHASE(10);
-    // zero the pad columns [N, GP) of every row (products, histogram, b)
-    if constexpr (GP > N) {
-        for (int i = tid; i < K * (GP - N); i += BLK) {
-            const int k = i / (GP - N), c = N + (i - k * (GP - N));
-            tab_put<PT, GP, LAY>(sP, sH, k * GP + c, 0.0, 0.0, 0.0);
-        }
-    }
-    __syncthreads();
-    double S = 0.0;
-#pragma unroll
-    for (int w = 0; w < NW; ++w) S += sSum[w];
-    const double L = m.local_lse ? ((S > 0.0) ? Mb + log(S) : -INFINITY) : sLr;
-    const double diff = (sIn.prev_L != -INFINITY) ? fabs(L - sIn.prev_L) : INFINITY;  // :505-508
-    const bool cont = (diff >= sIn.epsilon) && (sIn.iteration + 1 < sIn.max_iterations);  // :346
-    if (w0) {
-        if (tid < N) m.pi[tid] = sPA[tid];
-        if (tid < N * N) m.A[tid] = sPA[G + tid];
-        if (tid == 0) record_iteration(m, sIn, L);
-    }
-    return cont;
 }
 
 }  // namespace hmmbw

@@ -7,7 +7,7 @@
 // The pointers returned here are the kernels' host stubs, registered by their own unit's module.
 #pragma once
 
-#include "hmmbw_device.hpp"
+#include "hmmbw_args.hpp"
 
 namespace hmmbw {
 

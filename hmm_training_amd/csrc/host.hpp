@@ -9,13 +9,19 @@
 
 #include <algorithm>
 #include <climits>
+#include <cmath>
+#include <cstdio>
 #include <cstdlib>
+#include <cstring>
+#include <numeric>
 #include <string>
 #include <vector>
 #include <rccl/rccl.h>
 
-#include "hmmbw_device.hpp"
+#include "hmmbw_args.hpp"
 #include "hmmbw_kernels.hpp"
+#include "lds_layout.hpp"
+#include "obs_plan.hpp"
 #include "viterbi_plan.hpp"
 
 namespace hmmbw {
@@ -229,15 +235,15 @@ struct hmmbw_ctx {
     long long off_ll() const { return off_bnum() + (long long)K * N; }
     long long stats_len() const { return off_ll() + 2LL * world; }
     long long copy_len() const { return off_ll(); }
-    // emission P/H tables in LDS (two [K][G + kTabPad] tables of 16-B entries kHistOff bytes apart, see
+    // emission P/H tables in LDS (two [K][G] tables of 16-B entries kHistOff bytes apart, see
     // hmmbw_device.hpp) when the first fits below kHistOff (the row offsets then fit the uint16 packs)
-    bool lds_tables() const { return !wide && lds_tables_fit(K, G + kTabPad); }
+    bool lds_tables() const { return !wide && lds_tables_fit(K, G); }
     // LDS doubles of the small kernels' tables
-    size_t lds_table_doubles() const { return lds_tables() ? lds_table_bytes(K, G + kTabPad) / sizeof(double) : 0; }
+    size_t lds_table_doubles() const { return lds_tables() ? lds_table_bytes(K, G) / sizeof(double) : 0; }
     // the class-split tables (lds_layout.hpp, lay2_p_off) can serve this context's joined launches: G = 8,
     // the rows of one class within 64 KiB (uint16 packs); both classes then fit the CU's 160 KiB with the scratch
     bool split_tables() const {
-        return sw.lds_layout != 0 && !wide && !det && kTabPad == 0 && G == 8 && lds_tables() && lay2_tables_fit(K, G);
+        return sw.lds_layout != 0 && !wide && !det && G == 8 && lds_tables() && lay2_tables_fit(K, G);
     }
     size_t split_table_doubles() const { return lay2_table_bytes(K, G) / sizeof(double); }
     bool can_merge() const { return merge_mstep && lds_tables() && copy_len() <= kMergedMaxStats && nwaves > 0; }

@@ -1,4 +1,5 @@
-// lds_layout.hpp — address functions of the class-split LDS emission tables (hmmbw_device.hpp, LAY = 1).
+// lds_layout.hpp — geometry of the small kernels' LDS emission tables (hmmbw_device.hpp): the row layout's
+// table distance and sizes, and the address functions of the class-split layout (LAY = 1).
 // Plain constexpr C++ with no HIP dependency, so that a host compiler can build a probe of them
 // (tests/native/lds_layout_probe.cpp).
 #pragma once
@@ -12,6 +13,12 @@
 #endif
 
 namespace hmmbw {
+
+// The row layout (LAY = 0): two [K][G] tables of 16-B entries, the H-table kHistOff bytes after the P-table.
+// The kernels use them when the P-table fits below kHistOff (the row offsets then fit the uint16 symbol packs).
+constexpr int kHistOff = 32768;
+HMMBW_HD constexpr bool lds_tables_fit(int K, int GP) { return (size_t)K * GP * 16 <= (size_t)kHistOff; }
+HMMBW_HD constexpr size_t lds_table_bytes(int K, int GP) { return (size_t)kHistOff + (size_t)K * GP * 16; }
 
 // The class-split layout (LAY = 1) of the joined map's G = 8 kernels (k_estep_join<.., 1>), which own a whole
 // CU's LDS.  In the row layout (hmmbw_device.hpp) a ds_read_b128 lane group ({0-3, 12-15, 20-27}, ... MI355X: four 16-B windows

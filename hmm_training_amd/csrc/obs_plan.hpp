@@ -22,7 +22,7 @@ constexpr int kBlock = 256;  // threads per E-step workgroup (4 waves)
 constexpr int kWpb = kBlock / kWave;  // waves of a full (sequence-group) workgroup
 
 // ---------------------------------------------------------------------------------------------
-// Observation layout (hmmbw_device.hpp, struct Layout)
+// Observation layout (hmmbw_args.hpp, struct Layout)
 // ---------------------------------------------------------------------------------------------
 
 // index in a wave's symbol pack ([chunk][u][8] uint16 from symoff) of step t of the wave's sequence slot u
@@ -233,9 +233,6 @@ inline LaunchMap plan_map(const MapInputs &in) {
 // that host an extra workgroup.  cfg3: 32.2 -> 30.9 us per iteration (profiles/r5/join_ab.txt).
 // Round 6: the dense E-step joins too (HMMBW_JOIN_DENSE=0 keeps its separate extra workgroups); its split B
 // waves take A's hand-over through an LDS flag, so the joined workgroup's full waves are never held.
-#ifndef HMMBW_JOIN_ALL
-#define HMMBW_JOIN_ALL 1
-#endif
 // topo: the resolved topology (HMMBW_TOPOLOGY_DENSE or _LEFT_TO_RIGHT)
 inline bool joined(const LaunchMap &m, int topo) {
     const bool topo_ok = topo == HMMBW_TOPOLOGY_LEFT_TO_RIGHT || (topo == HMMBW_TOPOLOGY_DENSE && m.sw.join_dense);
@@ -243,7 +240,7 @@ inline bool joined(const LaunchMap &m, int topo) {
     // Round 6: left-to-right without extra groups too (at most 4 groups per CU, one workgroup per CU), the idle waves
     // 4-7 then only sharing the prologue's table build and the flush: T = 8 at 8,192 sequences 13.51 -> 12.96 us,
     // 8,192 x 200 27.59 -> 27.32, 4,096 x 200 24.30 -> 23.72 (profiles/r6/join_all_ab.txt)
-    const bool all = HMMBW_JOIN_ALL && topo == HMMBW_TOPOLOGY_LEFT_TO_RIGHT && m.nblocks == m.nfull && m.fits_cus;
+    const bool all = topo == HMMBW_TOPOLOGY_LEFT_TO_RIGHT && m.nblocks == m.nfull && m.fits_cus;
     return m.sw.join && topo_ok && m.lds_atomic && (m.nblocks > m.nfull || all) && m.nblocks - m.nfull <= m.nfull &&
            xw <= kWpb;
 }

@@ -17,6 +17,7 @@
 // addresses do not depend on the path, lane j holds psi_t(j)), so the dependent step is a cross-lane pick
 // s_{t-1} = psi_t[lane s_t], never a memory access.
 #include "host.hpp"
+#include "lane_ops.hpp"
 
 namespace hmmbw {
 
@@ -300,7 +301,7 @@ extern "C" int hmmbw_viterbi(hmmbw_ctx *c, double *logp_out, int32_t *path_out, 
     a.U = c->U;
     a.N = c->N;
     a.K = c->K;
-    const long long div = viterbi_pack_div(c->lds_tables(), c->G, kTabPad);
+    const long long div = viterbi_pack_div(c->lds_tables(), c->G, 0);  // rows of G entries, no pad column
     a.div = (int)div;
     a.shift = viterbi_pack_shift(div);
     const bool lds = viterbi_table_in_lds(c->K, P.GV);

@@ -48,7 +48,7 @@ def split_table_bytes(K, GP):
 
 
 def split_p_off(GP, cls, o, j):
-    """Byte offset of the P entry of (class, symbol, state column): mirrors lay2_p_off (hmmbw_device.hpp)."""
+    """Byte offset of the P entry of (class, symbol, state column): mirrors lay2_p_off (lds_layout.hpp)."""
     return cls * split_class_off(GP) + o * split_row_bytes(GP) + j * 16
 
 
