@@ -6,7 +6,7 @@ the EM hot path runs in hand-written gfx950 HIP kernels behind the C ABI of incl
 from .hmm_classes import DataStorageHMM, HMMTrained  # noqa: F401
 
 __all__ = ["HMMTrained", "DataStorageHMM", "hmm_training", "training_with_save", "get_observations",
-           "calculate_log_likelihood", "viterbi_decode", "BaumWelchEngine"]
+           "calculate_log_likelihood", "viterbi_decode", "posterior_decode", "BaumWelchEngine"]
 
 
 def __getattr__(name):
@@ -14,7 +14,7 @@ def __getattr__(name):
     if name in ("hmm_training", "training_with_save", "get_observations", "safe_log", "safe_exp", "log_sum_exp"):
         from . import hmm_training as _ht
         return getattr(_ht, name)
-    if name in ("calculate_log_likelihood", "score_matrix", "test_hmm", "viterbi_decode"):
+    if name in ("calculate_log_likelihood", "score_matrix", "test_hmm", "viterbi_decode", "posterior_decode"):
         from . import hmm_testing as _te
         return getattr(_te, name)
     if name == "BaumWelchEngine":

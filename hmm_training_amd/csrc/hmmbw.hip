@@ -258,6 +258,7 @@ static void free_obs(hmmbw_ctx *c) {
     dfree(c->d_ck); dfree(c->d_sp); dfree(c->d_ebuf); dfree(c->d_logp); dfree(c->d_llpart); dfree(c->d_zf);
     dfree(c->d_gam); dfree(c->d_bptr); dfree(c->d_brows); dfree(c->d_part); dfree(c->d_wq);
     viterbi_free(c);
+    posterior_free(c);
     c->wq_grid = 0;
     c->has_obs = false;
 }

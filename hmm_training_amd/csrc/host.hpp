@@ -1,7 +1,8 @@
 // host.hpp — what the host-side units share (internal; declarations only): the error channel, the
 // allocator's interface, the timing event pool, the launch plan, the context and the few helpers that
 // cross units.  Owners: alloc.hip (block cache, ledger), peer.hip (peer all-reduce), comm.hip (RCCL),
-// group.hip (grouped launches), viterbi.hip (hmmbw_viterbi and its kernels), hmmbw.hip (everything else, and the
+// group.hip (grouped launches), viterbi.hip (hmmbw_viterbi and its kernels), posterior.hip (hmmbw_posterior and
+// its kernels), hmmbw.hip (everything else, and the
 // definitions of the helpers below).
 // The observation layout and the launch map hmmbw.hip plans are obs_plan.hpp's: pure, shared with the
 // kernels, tested without a GPU (tests/test_obs_plan.py).
@@ -173,6 +174,13 @@ struct hmmbw_ctx {
         int32_t *d_path = nullptr;        // with paths only: caller CSR order
         unsigned char *d_psi = nullptr;   // with paths only: back-pointers, [t][64 lanes] bytes per decoding wave
     } vit;
+    // hmmbw_posterior (posterior.hip): it shares the decoder's plan, offsets and device logp; its own buffers are
+    // allocated on first use and freed with the observations
+    struct Posterior {
+        double *d_tab = nullptr;      // [GV] pi | [GV][GV] A row-major | [K][GV] B^T, linear, 0 in states >= N
+        double *d_scratch = nullptr;  // [total][N]: the alpha_hat -> gamma workspace of calls without gamma_dev
+        int32_t *d_path = nullptr;    // with paths only: caller CSR order
+    } post;
     // native RCCL communicator (hmmbw_comm_init): the multi-rank hmmbw_iterate all-reduces d_ext
     ncclComm_t comm = nullptr;
     double *d_ext = nullptr;      // non-fused multi-rank paths: the packed statistics to all-reduce
@@ -283,6 +291,10 @@ int launch_estep(hmmbw_ctx *c, bool fwd_only, const IterState *state, double *co
 
 // viterbi.hip
 void viterbi_free(hmmbw_ctx *c);  // the decoder's buffers; callers synchronise the context first
+int viterbi_plan_ready(hmmbw_ctx *c);  // c->vit.plan, d_slot_out and d_logp of the loaded observations (made once)
+
+// posterior.hip
+void posterior_free(hmmbw_ctx *c);  // hmmbw_posterior's buffers; callers synchronise the context first
 
 // peer.hip
 std::string peer_off_msg(const hmmbw_ctx *c);

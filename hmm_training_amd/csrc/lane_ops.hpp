@@ -105,6 +105,14 @@ __device__ __forceinline__ int gmax_i32(int e) {
     if constexpr (G >= 4) e = max(e, dpp_i32<0x4E>(e));
     if constexpr (G >= 8) e = max(e, dpp_i32<0x141>(e));
     if constexpr (G >= 16) e = max(e, dpp_i32<0x140>(e));
+    if constexpr (G >= 32) {  // across rows: lane ^ 16, then lane ^ 32 (the posterior kernels' 32- and 64-lane groups)
+        const auto r = __builtin_amdgcn_permlane16_swap((unsigned)e, (unsigned)e, false, false);
+        e = max((int)r[0], (int)r[1]);
+    }
+    if constexpr (G >= 64) {
+        const auto r = __builtin_amdgcn_permlane32_swap((unsigned)e, (unsigned)e, false, false);
+        e = max((int)r[0], (int)r[1]);
+    }
     return e;
 }
 
@@ -130,6 +138,26 @@ __device__ __forceinline__ double gbcast(double v, int lane) {
     } else {
         static_assert(G == 16, "group size");
         return dpp<0x150 + I>(v);  // row_newbcast:I
+    }
+}
+
+__device__ __forceinline__ double readlane_f64(double v, int l) {
+    const int lo = __builtin_amdgcn_readlane(__double2loint(v), l);
+    const int hi = __builtin_amdgcn_readlane(__double2hiint(v), l);
+    return __hiloint2double(hi, lo);
+}
+
+// Value of lane I of this lane's GV-group for the groups of the decoder and the posterior kernels
+// (viterbi_plan.hpp: 8, 16, 32 or 64 lanes): DPP up to 16 lanes, v_readlane for 32 and 64.
+template <int GV, int I>
+__device__ __forceinline__ double gbcast_wide(double v, int lane) {
+    if constexpr (GV <= 16) {
+        return gbcast<GV, I>(v, lane);
+    } else if constexpr (GV == 32) {
+        const double lo = readlane_f64(v, I), hi = readlane_f64(v, 32 + I);
+        return (lane & 32) ? hi : lo;
+    } else {
+        return readlane_f64(v, I);
     }
 }
 

@@ -57,30 +57,11 @@ __global__ void __launch_bounds__(256) k_viterbi_prep(const double *__restrict__
     }
 }
 
-__device__ __forceinline__ double readlane_f64(double v, int l) {
-    const int lo = __builtin_amdgcn_readlane(__double2loint(v), l);
-    const int hi = __builtin_amdgcn_readlane(__double2hiint(v), l);
-    return __hiloint2double(hi, lo);
-}
-
 // max of two doubles that are never NaN: the one instruction (fmax adds a canonicalising v_max_f64 of its own)
 __device__ __forceinline__ double vmax_f64(double a, double b) {
     double r;
     asm("v_max_f64 %0, %1, %2" : "=v"(r) : "v"(a), "v"(b));
     return r;
-}
-
-// value of lane I of this lane's GV-group
-template <int GV, int I>
-__device__ __forceinline__ double vit_bcast(double v, int lane) {
-    if constexpr (GV <= 16) {
-        return gbcast<GV, I>(v, lane);
-    } else if constexpr (GV == 32) {
-        const double lo = readlane_f64(v, I), hi = readlane_f64(v, 32 + I);
-        return (lane & 32) ? hi : lo;
-    } else {
-        return readlane_f64(v, I);
-    }
 }
 
 template <int GV, bool LR, bool PATH, bool LDSTAB>
@@ -149,12 +130,12 @@ __global__ void __launch_bounds__(kVitBlock) k_viterbi(VArgs a) {
                 // straight-line blocks of up to 16 candidates; a block wholly past N is skipped (wave-uniform), the
                 // padded candidates of a block are -inf + -inf and never win
                 constexpr int BLK = GV < 16 ? GV : 16;
-                best = vit_bcast<GV, 0>(delta, lane) + la[0];
+                best = gbcast_wide<GV,0>(delta, lane) + la[0];
                 sfor<0, GV / BLK>([&](auto Bk) {
                     constexpr int b = decltype(Bk)::value;
                     if (b == 0 || b * BLK < a.N) {
                         sfor<(b == 0 ? 1 : b * BLK), (b + 1) * BLK>([&](auto I) {
-                            const double c = vit_bcast<GV, I>(delta, lane) + la[I];
+                            const double c = gbcast_wide<GV,I>(delta, lane) + la[I];
                             arg = c > best ? (int)I : arg;
                             best = vmax_f64(best, c);
                         });
@@ -227,9 +208,9 @@ void viterbi_free(hmmbw_ctx *c) {
     v.plan = ViterbiPlan{};
 }
 
-// the decoder's buffers for the loaded observations: the tables, the offsets and the device logp on the
-// first decode, the path and the back-pointers on the first decode with paths
-static int viterbi_buffers(hmmbw_ctx *c, bool path) {
+// the plan of the loaded observations with its offsets on the device, the log tables and the device logp: made
+// by the first decode or the first hmmbw_posterior (posterior.hip shares the plan, the offsets and the logp)
+int viterbi_plan_ready(hmmbw_ctx *c) {
     hmmbw_ctx::Viterbi &v = c->vit;
     if (!v.planned) {
         viterbi_free(c);  // what a failed earlier attempt left
@@ -252,6 +233,14 @@ static int viterbi_buffers(hmmbw_ctx *c, bool path) {
         v.plan = P;
         v.planned = true;
     }
+    return HMMBW_OK;
+}
+
+// the decoder's buffers for the loaded observations: the plan on the first decode, the path and the
+// back-pointers on the first decode with paths
+static int viterbi_buffers(hmmbw_ctx *c, bool path) {
+    if (int rc = viterbi_plan_ready(c)) return rc;
+    hmmbw_ctx::Viterbi &v = c->vit;
     if (path && !v.d_path) {
         int rc = dalloc(&v.d_path, (size_t)v.plan.total);
         if (!rc) rc = dalloc(&v.d_psi, (size_t)v.plan.psi_rows * kVitWave);

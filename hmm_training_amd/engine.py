@@ -559,6 +559,23 @@ class BaumWelchEngine:
             return None, logp[: self.n_seq]
         return np.split(flat[:total], self._offsets[1:-1]) if self.n_seq else [], logp[: self.n_seq]
 
+    def posterior(self, gamma: bool = True, paths: bool = True):
+        """Smoothed state posteriors of every loaded sequence under the current parameters (hmmbw_posterior):
+        (gamma, paths, logp).  gamma: a torch.float64 tensor [total symbols, N] on the engine's device, caller CSR
+        order (row offsets[r] + t is gamma_t of sequence r), or None with gamma=False; paths: one int32 array per
+        sequence, the state with the largest gamma at every step (the lowest on ties), or None with paths=False;
+        logp: log P(O_r | lambda).  A sequence with P(O) = 0 has logp -inf, zero rows and a path of -1."""
+        total = getattr(self, "n_symbols_total", 0)
+        logp = np.zeros(max(self.n_seq, 1))
+        g = torch.empty((total, self.N), dtype=torch.float64, device=f"cuda:{self.device}") if gamma else None
+        flat = np.zeros(max(total, 1), dtype=np.int32) if paths else None
+        check(self._lib.hmmbw_posterior(self._ctx, ctypes.c_void_p(g.data_ptr()) if gamma and total else None,
+                                        total * self.N, flat.ctypes.data if paths else None, total, logp.ctypes.data))
+        split = None
+        if paths:
+            split = np.split(flat[:total], self._offsets[1:-1]) if self.n_seq else []
+        return g, split, logp[: self.n_seq]
+
     def timing(self, enable: int = -1) -> Tuple[float, int]:
         """(accumulated E-step ms, timed launches) of hmmbw_timing; enable >= 0 also resets and sets the
         mode (0 off, k: every k-th launch), enable < 0 only queries."""

@@ -68,6 +68,22 @@ def viterbi_decode(observations: Sequence[np.ndarray], hmm: HMMTrained, device=N
         return eng.viterbi()
 
 
+def posterior_decode(observations: Sequence[np.ndarray], hmm: HMMTrained,
+                     device=None) -> Tuple[List[np.ndarray], List[np.ndarray], np.ndarray]:
+    """(gammas, paths, logp): the smoothed state posteriors gamma_t(i) = P(q_t = i | O, lambda) of every recording
+    under one model as host [T_r, N] arrays, the state with the largest gamma at every step, and log P(O | lambda),
+    all sequences in one launch (BaumWelchEngine.posterior).  A sequence with P(O) = 0 has logp -inf, zero rows
+    and a path of -1."""
+    if len(observations) == 0:
+        return [], [], np.zeros(0)
+    N, M = int(hmm.states), int(np.asarray(hmm.B).shape[1])
+    with BaumWelchEngine(N, M, device=device) as eng:
+        eng.set_observations(observations)
+        eng.set_params(np.asarray(hmm.Pi), np.asarray(hmm.A), np.asarray(hmm.B))
+        gamma, paths, logp = eng.posterior()
+        return np.split(gamma.cpu().numpy(), eng._offsets[1:-1]), paths, logp
+
+
 def calculate_log_likelihood(recording_observations: np.ndarray, hmm: HMMTrained) -> float:
     """log P(O | lambda) of one sequence under one linear-domain model (hmm_testing.py:49-104)."""
     return float(score_matrix([np.asarray(recording_observations)], [hmm])[0, 0])

@@ -39,7 +39,8 @@ extern "C" {
                                  (HMMBW_OPT_LDS_LAYOUT / HMMBW_INFO_LDS_LAYOUT are new keys of the same calls:
                                  an older library answers them HMMBW_E_INVALID, no entry point changed;
                                  hmmbw_viterbi is a new entry point of version 5: an older library lacks the
-                                 symbol) */
+                                 symbol; hmmbw_posterior is a new entry point of version 5: an older library
+                                 lacks the symbol) */
 
 #define HMMBW_OK 0
 #define HMMBW_E_INVALID (-1)        /* bad argument (shape, range, null pointer)             */
@@ -249,6 +250,24 @@ int hmmbw_score(hmmbw_ctx *ctx, double *out);
  * Any context (1 <= N <= 64, both topologies); a multi-rank context decodes its own shard, no collective.
  * Leaves the log-likelihoods of hmmbw_get_loglik, the statistics and the training state as they were. */
 int hmmbw_viterbi(hmmbw_ctx *ctx, double *logp_out, int32_t *path_out, int64_t path_len);
+
+/* SYNC. Smoothed state posteriors of the loaded sequences under the current parameters:
+ *   gamma_t(i) = alpha_t(i) beta_t(i) / P(O)            (hmm_training.py:388-394, linear domain)
+ * gamma_dev (DEVICE pointer, may be NULL): [total symbols][N] doubles, row-major, caller CSR order,
+ *   gamma_dev[(offsets[r] + t) * N + i]; gamma_len must be total * N.
+ * path_out (HOST, may be NULL): int32, caller CSR order, the SMALLEST i attaining max_i gamma_t(i);
+ *   path_len must be the total number of loaded symbols.
+ * logp_out (HOST, may be NULL): R doubles, log P(O_r | lambda).
+ * A sequence with P(O) = 0: logp -inf, every gamma entry 0.0, every path entry -1.  No NaN anywhere.
+ * At least one output must be non-NULL.
+ * Both lengths are checked whether or not their pointer is NULL (HMMBW_E_INVALID), as hmmbw_viterbi checks
+ * path_len.  gamma_dev doubles as the workspace (the forward's scaled alpha rows are overwritten by gamma); without
+ * it, a call that asks for the path uses a buffer of the same size that the library keeps until the observations
+ * change.  A call that asks for logp_out alone runs the forward recursion only and stores no rows.
+ * Any context (1 <= N <= 64, both topologies); a multi-rank context handles its own shard, no collective.
+ * Leaves the log-likelihoods of hmmbw_get_loglik, the statistics and the training state as they were. */
+int hmmbw_posterior(hmmbw_ctx *ctx, double *gamma_dev, int64_t gamma_len,
+                    int32_t *path_out, int64_t path_len, double *logp_out);
 
 /* Engine knobs.  HMMBW_OPT_SAFE_SCALING = 1 forces the per-step power-of-two normalisation of the
  * forward recursion (default 0: lagged normalisation, automatic per-wave fallback to the per-step
