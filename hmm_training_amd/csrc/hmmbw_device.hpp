@@ -21,6 +21,8 @@
 namespace hmmbw {
 
 constexpr int kScale = 8;  // lagged mode: the forward rescales every kScale steps
+// the lagged mode's envelope: the scaled group exponent at every scale step within [-kLagLow, kLagHigh]
+constexpr int kLagLow = 450, kLagHigh = 900;
 
 // ---------------------------------------------------------------------------------------------
 // Small-N E-step / scorer.  One G-lane group per sequence (lane j = state j), 64/G per wave.
@@ -29,8 +31,19 @@ constexpr int kScale = 8;  // lagged mode: the forward rescales every kScale ste
 // kScale-th step rescales, by s_t = M_{t-kScale} - 1023 with M = the biased exponent of the group's
 // largest entry measured kScale steps earlier, so the per-step dependency chain is just
 // (DPP shift || multiply) -> fma; the scaling itself is folded into the emission factor
-// b_j(o_t) * 2^{-s_t} (exact).  If a wave's magnitudes ever leave [2^-900, 2^900]
-// (pathological parameters) the wave re-runs its forward in the safe mode, which normalises every
+// b_j(o_t) * 2^{-s_t} (exact).  The envelope of the lagged mode: at every scale step the group's largest
+// scaled entry lies within [2^-450, 2^900].  The lower bound is half of what fp64 would seem to allow because
+// the step's result BEFORE its rescale has the exponent (M_t - 1023) + s_t, and s_t = M_{t-kScale} - 1023
+// only undoes the decay measured up to t - kScale: that value carries the decay of the last 2 kScale steps.
+// With both terms at least -450 it is at least 2^-900.  (A run of floor-probability symbols, 1e-20 = 2^-66.4,
+// mstep.hpp, puts it at 2^-1063 after sixteen of them, an fp64 denormal, while the scaled exponent stays near
+// -530: a bound of -900 on the scaled exponent alone let such waves through with log P wrong in the 6th
+// digit and NaN statistics.)  A group's sum cannot grow inside an unscaled interval (emissions and transition
+// rows are at most 1), so the value at the interval's end bounds the whole interval from below to within a
+// factor N, and beta_hat ~ gamma / z of the backward recompute from above.  The steps after a sequence's
+// last scale step have no next one to speak for them: the final z_{T-1} itself is held to 2^-900 as well
+// (its sum is phat, and 1 / phat starts the backward).  A wave that leaves the
+// envelope (a dead sequence does: M = 0) re-runs its forward in the safe mode, which normalises every
 // step by its own group maximum.  Only z at the first step of every 8-step chunk (the checkpoint)
 // and the s_t are stored; the backward sweep recomputes each chunk's z_t in registers with the
 // identical instruction sequence (bit-identical), so alpha never round-trips through HBM.
@@ -684,7 +697,13 @@ __device__ __forceinline__ void estep_small_body(const EArgs &a, const long long
                     }
                 }
             }
-            return (!SAFE) && (minM < 1023 - 900 || maxM > 1023 + 900);
+            // the envelope (top of this section): kLagLow bounds the value before the next rescale, M + s, by
+            // twice itself.  No scale step follows the sequence's last one, so the steps after it (up to
+            // kScale - 1, unscaled) are bounded by their end, the final z (held from step T - 1 on in masked
+            // chunks): once per sweep, after it
+            if constexpr (SAFE) return false;
+            const int Mend = group_bexp(z);
+            return minM < 1023 - kLagLow || maxM > 1023 + kLagHigh || Mend < 1023 - 2 * kLagLow;
         };
         bool safe = a.force_safe != 0;
         if (!brole) {  // the B partner of a split group runs no forward

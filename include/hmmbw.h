@@ -271,7 +271,11 @@ int hmmbw_posterior(hmmbw_ctx *ctx, double *gamma_dev, int64_t gamma_len,
 
 /* Engine knobs.  HMMBW_OPT_SAFE_SCALING = 1 forces the per-step power-of-two normalisation of the
  * forward recursion (default 0: lagged normalisation, automatic per-wave fallback to the per-step
- * form when magnitudes leave [2^-900, 2^900]).  Results agree to fp64 rounding either way. */
+ * form when, at one of its rescaling steps, the scaled forward value leaves [2^-450, 2^900], or when the
+ * sequence's final value is below 2^-900.  The lower bound keeps the value before the next rescale, which
+ * carries the decay of the last sixteen steps, above 2^-900 (runs of symbols at the M-step's 1e-20 floor
+ * would otherwise take it into the fp64 denormals); the final value speaks for the steps that no rescaling
+ * step follows).  Results agree to fp64 rounding either way (tests/test_gpu_scaling.py). */
 #define HMMBW_OPT_SAFE_SCALING 1
 /* Diagnostics only (profiling ablations; results are WRONG while nonzero): bit 0 skips the E-step's
  * statistics flush, bit 1 skips its backward sweep, bit 2 skips the separate (unmerged) M-step kernel. */

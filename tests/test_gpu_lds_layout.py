@@ -25,15 +25,16 @@ def gpu():
         pytest.fail("no HIP device visible: the GPU tests need an MI355X")
 
 
-def run_case(oracle, obs, N, K, topology, layout, joined=None, split_extra=None, option=1):
+def run_case(oracle, obs, N, K, topology, layout, joined=None, split_extra=None, option=1, params=None):
     """Train ITERS iterations on `obs`, check everything against the oracle, assert the reported layout (and map);
-    returns (trace of L, log P, decoded statistics) for comparisons between contexts."""
+    returns (trace of L, log P, decoded statistics) for comparisons between contexts.  params: the starting
+    (pi, A, B) instead of the seeded default."""
     from hmm_training_amd._lib import OPT_LDS_LAYOUT
     from hmm_training_amd.engine import BaumWelchEngine, to_csr
     off, sym = to_csr(obs)
     sym64 = sym.astype(np.int64)
     R, total = len(obs), int(off[-1])
-    pi, A, B = _params(N, K, topology, 7)
+    pi, A, B = _params(N, K, topology, 7) if params is None else params
     ref = oracle.hmm_training(off, sym64, N, K, 0.0, ITERS, pi, A, B)
     with BaumWelchEngine(N, K, topology=topology) as eng:
         if option is not None:
