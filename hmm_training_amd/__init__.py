@@ -6,7 +6,8 @@ the EM hot path runs in hand-written gfx950 HIP kernels behind the C ABI of incl
 from .hmm_classes import DataStorageHMM, HMMTrained  # noqa: F401
 
 __all__ = ["HMMTrained", "DataStorageHMM", "hmm_training", "training_with_save", "get_observations",
-           "calculate_log_likelihood", "viterbi_decode", "posterior_decode", "BaumWelchEngine"]
+           "calculate_log_likelihood", "viterbi_decode", "posterior_decode", "BaumWelchEngine", "lbg_train",
+           "createCodeVector", "save_centroids"]
 
 
 def __getattr__(name):
@@ -17,6 +18,12 @@ def __getattr__(name):
     if name in ("calculate_log_likelihood", "score_matrix", "test_hmm", "viterbi_decode", "posterior_decode"):
         from . import hmm_testing as _te
         return getattr(_te, name)
+    if name in ("lbg_train", "createCodeVector", "LBGResult"):
+        from . import codevector as _cv
+        return getattr(_cv, name)
+    if name == "save_centroids":
+        from .io import save_centroids
+        return save_centroids
     if name == "BaumWelchEngine":
         from .engine import BaumWelchEngine
         return BaumWelchEngine

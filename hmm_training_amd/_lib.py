@@ -40,7 +40,7 @@ EXPORTED = (
     "hmmbw_comm_probe", "hmmbw_comm_info", "hmmbw_comm_payload", "hmmbw_iterate_begin", "hmmbw_iterate_end",
     "hmmbw_cache_trim", "hmmbw_timing_split", "hmmbw_peer_region", "hmmbw_peer_ipc_handle", "hmmbw_peer_open",
     "hmmbw_peer_attach", "hmmbw_allreduce_kind", "hmmbw_status_live_wait", "hmmbw_get_option", "hmmbw_viterbi",
-    "hmmbw_posterior",
+    "hmmbw_posterior", "hmmbw_lbg_train",
 )
 ABI_VERSION = 5
 OPT_SAFE_SCALING = 1
@@ -80,6 +80,11 @@ class IterRecord(ctypes.Structure):
 class Status(ctypes.Structure):
     _fields_ = [("iterations", ctypes.c_int64), ("done", ctypes.c_int32), ("converged", ctypes.c_int32),
                 ("last_log_likelihood", ctypes.c_double), ("last_diff", ctypes.c_double)]
+
+
+class LbgRecord(ctypes.Structure):
+    _fields_ = [("generation", ctypes.c_int32), ("iteration", ctypes.c_int32), ("distortion", ctypes.c_double),
+                ("diff", ctypes.c_double)]
 
 
 _lock = threading.Lock()
@@ -133,6 +138,10 @@ def _declare(lib):
         "hmmbw_vq_encode": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64, ctypes.c_int, ctypes.c_int,
                                            ctypes.c_int, ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p,
                                            ctypes.c_void_p]),
+        "hmmbw_lbg_train": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64, ctypes.c_int, ctypes.c_int,
+                                           ctypes.c_int, ctypes.c_int, ctypes.c_double, ctypes.c_int64, ctypes.c_double,
+                                           ctypes.c_double, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
+                                           ctypes.c_void_p, ctypes.c_int64, P(ctypes.c_int64)]),
         "hmmbw_comm_probe": (ctypes.c_int, [ctypes.c_char_p]),
         "hmmbw_comm_unique_id": (ctypes.c_int, [ctypes.c_char_p, ctypes.c_void_p]),
         "hmmbw_comm_init": (ctypes.c_int, [c_ctx, ctypes.c_char_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_int,

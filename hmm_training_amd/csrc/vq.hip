@@ -22,6 +22,8 @@
 #include <cmath>
 #include <cstdint>
 
+#include "vq_scan.hpp"
+
 namespace hmmbw {
 
 // DMAX = D (exact, the reference's 12 dims): the codebook is read with wave-uniform SCALAR loads
@@ -42,55 +44,9 @@ __global__ void __launch_bounds__(256) k_vq_encode_s(const double *__restrict__ 
 #pragma unroll
         for (int d = 0; d < D; ++d) x[q][d] = frames[f * stride + col0 + d];
     }
-    double best_s[FPL], best_d[FPL];
+    double best_s[FPL];
     int arg[FPL];
-#pragma unroll
-    for (int q = 0; q < FPL; ++q) {
-        best_s[q] = INFINITY;
-        best_d[q] = INFINITY;
-        arg[q] = 0;
-    }
-    const double *c = cents + col0;
-    // centroid k + 1's row is loaded (into SGPRs) while centroid k is scanned
-    double cn[D];
-#pragma unroll
-    for (int d = 0; d < D; ++d) cn[d] = c[d];
-    for (int k = 0; k < K; ++k) {
-        double cc[D];
-#pragma unroll
-        for (int d = 0; d < D; ++d) cc[d] = cn[d];
-        c += stride;
-        if (k + 1 < K) {
-#pragma unroll
-            for (int d = 0; d < D; ++d) cn[d] = c[d];
-        }
-        double acc[FPL];
-#pragma unroll
-        for (int d = 0; d < D; ++d)
-#pragma unroll
-            for (int q = 0; q < FPL; ++q) {
-                const double e = x[q][d] - cc[d];
-                acc[q] = (d == 0) ? e * e : __builtin_fma(e, e, acc[q]);
-            }
-        // only candidates with acc < best_d can have sqrt(acc) < best_s (sqrt is monotone); after the
-        // first few centroids that is rare, so the sqrt sits behind a real branch
-        bool any = false;
-#pragma unroll
-        for (int q = 0; q < FPL; ++q) any = any || (acc[q] < best_d[q]);
-        if (__builtin_expect(__any(any), 0)) {
-#pragma unroll
-            for (int q = 0; q < FPL; ++q) {
-                if (acc[q] < best_d[q]) {
-                    const double sq = __builtin_sqrt(acc[q]);
-                    if (sq < best_s[q]) {
-                        best_s[q] = sq;
-                        best_d[q] = acc[q];
-                        arg[q] = k;
-                    }
-                }
-            }
-        }
-    }
+    vq_scan_scalar<D, FPL>(x, cents + col0, stride, K, best_s, arg);
 #pragma unroll
     for (int q = 0; q < FPL; ++q) {
         if (f0 + q >= F) break;
@@ -105,36 +61,16 @@ __global__ void __launch_bounds__(256) k_vq_encode(const double *__restrict__ fr
                                                    int col0, int D, const double *__restrict__ cents, int K,
                                                    int *__restrict__ out, double *__restrict__ dist) {
     extern __shared__ double sC[];  // [K][D] codebook (columns col0 .. col0 + D)
-    for (int i = threadIdx.x; i < K * D; i += blockDim.x) {
-        const int k = i / D, d = i - k * D;
-        sC[i] = cents[(long long)k * stride + col0 + d];
-    }
+    vq_stage_codebook(sC, cents, stride, col0, D, K);
     __syncthreads();
     const long long f = (long long)blockIdx.x * blockDim.x + threadIdx.x;
     if (f >= F) return;
     double x[DMAX];
 #pragma unroll
     for (int d = 0; d < DMAX; ++d) x[d] = (d < D) ? frames[f * stride + col0 + d] : 0.0;
-    double best_s = INFINITY, best_d = INFINITY;
-    int arg = 0;
-    for (int k = 0; k < K; ++k) {
-        const double *c = sC + k * D;
-        double acc = 0.0;
-#pragma unroll
-        for (int d = 0; d < DMAX; ++d) {
-            if (d >= D) break;
-            const double e = x[d] - c[d];
-            acc = (d == 0) ? e * e : __builtin_fma(e, e, acc);
-        }
-        if (acc < best_d) {
-            const double s = __builtin_sqrt(acc);
-            if (s < best_s) {
-                best_s = s;
-                best_d = acc;
-                arg = k;
-            }
-        }
-    }
+    double best_s;
+    int arg;
+    vq_scan_lds<DMAX>(x, D, sC, K, best_s, arg);
     out[f] = arg;
     if (dist) dist[f] = best_s;
 }

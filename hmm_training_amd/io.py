@@ -38,6 +38,14 @@ def load_centroids(path: str) -> List[Centroid]:
             for i, d in enumerate(data)]
 
 
+def save_centroids(path: str, centroids) -> None:
+    """Write the codebook as DataStorage.save_centroids does (codevector_classes.py:548-556): a JSON list of
+    CentroidDataMFCC.to_dict() = ``{"mfcc": [...], "id": k}`` (:321-326) with indent 2, which load_centroids reads."""
+    data = [{"mfcc": np.asarray(c.mfcc, dtype=np.float64).reshape(-1).tolist(), "id": int(c.id)} for c in centroids]
+    with open(path, "w") as fh:
+        json.dump(data, fh, indent=2)
+
+
 def load_frames(path: str) -> List[Frame]:
     with open(path) as fh:
         data = json.load(fh)

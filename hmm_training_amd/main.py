@@ -1,7 +1,10 @@
-"""``train`` / ``test`` entry points of the reference's HMM/main.py (:46-197) on the MI355X engine.
+"""``train`` / ``test`` entry points of the reference's HMM/main.py (:46-197) on the MI355X engine, and
+``codebook``, the LBG training of the codebook they read (the reference's CodeVector pipeline).
 
     python -m hmm_training_amd.main train [--max-iterations 2] [--data ../Data]
     python -m hmm_training_amd.main test  [--data ../Data]
+    python -m hmm_training_amd.main codebook --frames PATH [PATH ...] --out codevector.json
+                                             [--centroids 256 --max-iterations 100 --epsilon 0.001]
 
 Same on-disk layout as the reference:
 * ``<data>/CodeVector/codevector.json`` — the codebook;
@@ -33,7 +36,7 @@ from typing import Dict, List, Optional
 from .hmm_classes import DataStorageHMM, HMMTrained
 from .hmm_testing import test_hmm
 from .hmm_training import get_observations, hmm_training_group, training_with_save
-from .io import Centroid, Frame, load_centroids, load_frames
+from .io import Centroid, Frame, load_centroids, load_frames, save_centroids
 
 logger = logging.getLogger(__name__)
 
@@ -187,16 +190,48 @@ def test(show_progress=False, base_dir="../Data", model_dir: Optional[str] = Non
     return true_labels, predicted
 
 
+def codebook(frame_paths: List[str], out: str, centroids_quantity: int = 256, max_iterations: int = 100,
+             epsilon: float = 0.001) -> List[Centroid]:
+    """Train the codebook on the frames of every ``*_frames.json`` in ``frame_paths`` (createCodeVector on the
+    GPU) and write it to ``out`` in the codevector.json format."""
+    from .codevector import createCodeVector
+    frames: List[Frame] = []
+    for path in frame_paths:
+        loaded = load_frames(path)
+        print(f"Loaded {len(loaded)} frames from {path}")
+        frames.extend(loaded)
+    centroids, _ = createCodeVector(frames, centroids_quantity=centroids_quantity, max_iterations=max_iterations,
+                                    epsilon=epsilon, save_updates=False)
+    out_dir = os.path.dirname(os.path.abspath(out))
+    os.makedirs(out_dir, exist_ok=True)
+    save_centroids(out, centroids)
+    print(f"Saved {len(centroids)} centroids to {out}")
+    return centroids
+
+
 def _cli(argv=None):
     ap = argparse.ArgumentParser(description=__doc__.splitlines()[0])
-    ap.add_argument("command", choices=["train", "test"])
+    ap.add_argument("command", choices=["train", "test", "codebook"])
     ap.add_argument("--data", default="../Data")
     ap.add_argument("--models", default=None, help="model directory (default: DataStorageHMM's)")
-    # `python main.py train` runs train_hmm(show_progress=True, max_iterations=2) (HMM/main.py:268)
-    ap.add_argument("--max-iterations", type=int, default=2)
+    # `python main.py train` runs train_hmm(show_progress=True, max_iterations=2) (HMM/main.py:268);
+    # codebook: createCodeVector's default of 100
+    ap.add_argument("--max-iterations", type=int, default=None)
     ap.add_argument("--load-initial-params", action="store_true")
     ap.add_argument("--quiet", action="store_true")
+    ap.add_argument("--frames", nargs="+", default=None, help="codebook: *_frames.json files to train on")
+    ap.add_argument("--out", default=None, help="codebook: the codevector.json to write")
+    ap.add_argument("--centroids", type=int, default=256)
+    ap.add_argument("--epsilon", type=float, default=0.001)
     a = ap.parse_args(argv)
+    if a.command == "codebook":
+        if not a.frames or not a.out:
+            ap.error("codebook needs --frames and --out")
+        codebook(a.frames, a.out, centroids_quantity=a.centroids,
+                 max_iterations=100 if a.max_iterations is None else a.max_iterations, epsilon=a.epsilon)
+        return 0
+    if a.max_iterations is None:
+        a.max_iterations = 2
     if a.command == "train":
         ok = train_hmm(show_progress=not a.quiet, max_iterations=a.max_iterations,
                        load_initial_params=a.load_initial_params, base_dir=a.data, model_dir=a.models)

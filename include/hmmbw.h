@@ -40,7 +40,8 @@ extern "C" {
                                  an older library answers them HMMBW_E_INVALID, no entry point changed;
                                  hmmbw_viterbi is a new entry point of version 5: an older library lacks the
                                  symbol; hmmbw_posterior is a new entry point of version 5: an older library
-                                 lacks the symbol) */
+                                 lacks the symbol; hmmbw_lbg_train is a new entry point of version 5: an older
+                                 library lacks the symbol) */
 
 #define HMMBW_OK 0
 #define HMMBW_E_INVALID (-1)        /* bad argument (shape, range, null pointer)             */
@@ -387,6 +388,39 @@ int hmmbw_timing_split(hmmbw_ctx *ctx, double *estep_ms, int64_t *count);
  * legacy default), asynchronous; the device is the current one.  Codebook <= 160 KiB. */
 int hmmbw_vq_encode(void *stream, const double *frames, int64_t n_frames, int frame_stride, int first_dim, int dims,
                     const double *centroids, int n_centroids, int32_t *symbols, double *distances);
+
+/* ---- LBG codebook training: the step that produces the codebook hmmbw_vq_encode reads ----
+ * createCodeVector, CodeVector/codevector_functions.py:442-531 (the MFCC variant): c0 is the mean of all frames over
+ * all frame_stride columns; each of the G = log2(n_centroids) generations starts from the split of the one before
+ * (row i -> rows 2i = c * split_up and 2i + 1 = c * split_down, the reference's 1.001 and 0.999) and repeats
+ * "assign every frame to its nearest centroid over the columns [first_dim, first_dim + dims) (hmmbw_vq_encode's
+ * arithmetic and tie rule), distortion = sum of the winning distances, centroid k = mean over all columns of its
+ * frames (zeros when it has none), diff = |previous distortion - distortion|" while diff > epsilon and fewer than
+ * max_iterations passes were made; a NaN diff ends the generation, as in the reference.  The order in which the
+ * centroid sums and the distortion are added up is unspecified (floating-point atomics).
+ * All passes run on the device: an assign-and-accumulate kernel and a one-workgroup update kernel per pass, the
+ * latter advancing a device-side state (generation, pass, previous distortion, centroids in use, done); the host
+ * enqueues passes in chunks and reads the state between chunks.
+ * DEVICE pointers: frames [n_frames][frame_stride]; centroids [n_centroids][frame_stride], the last generation;
+ * generations (or NULL) [2 n_centroids - 1][frame_stride]: c0, then generation 1 (2 rows), ... generation G, each as
+ * it stood at the end of its loop; assignments (or NULL) int32 [n_frames]: the LAST pass's, made against the
+ * centroids before the last update.  HOST: records (or NULL) gets the first records_cap passes, *n_records (or NULL)
+ * the number of passes made.  SYNCHRONOUS on `stream` (hipStream_t, NULL = legacy default); the device is the
+ * current one; the workspace comes from the library's block cache.
+ * HMMBW_E_INVALID: n_frames < 1, n_centroids not a power of two >= 2, dims < 1, first_dim < 0, first_dim + dims >
+ * frame_stride, max_iterations < 1, epsilon negative or NaN, frames or centroids NULL.  HMMBW_E_UNSUPPORTED: the per-workgroup LDS, 8 (1 + n_centroids (frame_stride + 1)) bytes of
+ * accumulators plus, for dims != 12, the staged codebook 8 n_centroids dims, exceeds 160 KiB (n_centroids = 1024
+ * at stride 13 and dims 12 takes 112 KiB); dims > 64 other than through the dims == 12 scan. */
+typedef struct {
+    int32_t generation; /* 1 .. G */
+    int32_t iteration;  /* pass within the generation, from 1 */
+    double distortion;  /* sum of the winning distances of the pass */
+    double diff;        /* |distortion of the pass before - distortion| (0 before a generation's first) */
+} hmmbw_lbg_record;
+int hmmbw_lbg_train(void *stream, const double *frames, int64_t n_frames, int frame_stride, int first_dim, int dims,
+                    int n_centroids, double epsilon, int64_t max_iterations, double split_up, double split_down,
+                    double *centroids, double *generations, int32_t *assignments,
+                    hmmbw_lbg_record *records, int64_t records_cap, int64_t *n_records);
 
 /* ---- Groups: several models of one shape, one launch per EM iteration / per scoring pass ----
  * The reference trains its word models one after another (train_hmm, HMM/main.py:147-152, calling
