@@ -90,7 +90,12 @@ __device__ __forceinline__ void touch_kernargs() {
 // against 73.4), and H entries {h, h'} with the even / odd sequence slots adding into their own half (a
 // ds_add_f64 serves 16 contiguous lanes = two slots x 8 states, and both slots' adds otherwise hit the same
 // 8 even banks), b(o_0) then coming from the statistics: LR cfg3 36.96-36.98 us against 35.23-35.58.
-// LAY = 1, the class-split layout: both classes' copies of the entry (see lay2_p_off).
+// (That was on these row tables, 4-wave workgroups two to a CU, b(o_0) fetched from HBM.  The class-split
+// layout of the joined kernel does take the {h, h'} entries, round 10: it owns the CU's LDS, so b sits in a
+// table of its own there, and the adds were its largest LDS consumer: about 0.4 us faster at cfg3, 28.0 ->
+// 27.6 us, profiles/r10/hist_parity_ab.txt.  The row tables have no LDS for a b table at two workgroups per CU.)
+// LAY = 1, the class-split layout: both classes' copies of the entry (see lay2_p_off), their H entries the two
+// zeroed histogram halves {h_even, h_odd} (lay2_add_off), and for PT b in the b table sH[i] (lay2_b_off).
 template <bool PT, int GP, int LAY = 0>
 __device__ __forceinline__ void tab_put(double *sP, double *sH, int i, double px, double py, double b) {
     const double2 p = PT ? double2{px, py} : double2{b, 0.0};
@@ -103,8 +108,9 @@ __device__ __forceinline__ void tab_put(double *sP, double *sH, int i, double px
 #pragma unroll
         for (int cls = 0; cls < 2; ++cls) {
             *reinterpret_cast<double2 *>(e + cls * lay2_class_off(GP)) = p;
-            *reinterpret_cast<double2 *>(e + cls * lay2_class_off(GP) + lay2_hist_off(GP)) = double2{0.0, b};
+            *reinterpret_cast<double2 *>(e + cls * lay2_class_off(GP) + lay2_hist_off(GP)) = double2{0.0, 0.0};  // both halves
         }
+        if constexpr (PT) sH[i] = b;  // the compact b table (lay2_b_off); dense reads b from its P entry
     }
 }
 
@@ -310,6 +316,7 @@ __device__ __forceinline__ void estep_small_body(const EArgs &a, const long long
     static_assert(!JOIN || (BLK == 2 * kBlock && LDSTAB && !FWD_ONLY && !DET), "joined map: E-step with LDS tables");
     static_assert(LAY == 0 || (LAY == 1 && JOIN && G == 8), "class-split tables: joined map, G = 8");
     // H entry - P entry of a lane's step address: the immediate offset of the histogram add and the H.b read
+    // (class-split tables: the add has a lane address of its own, lay2_add_off, and b a table of its own)
     constexpr int HOFF = LAY ? lay2_hist_off(G) : kHistOff;
     constexpr int U = kWave / G;
     // dense G = 8: xi on the 4x4x4 MFMA (xi_mfma8), two accumulators per lane in its D layout
@@ -348,8 +355,9 @@ __device__ __forceinline__ void estep_small_body(const EArgs &a, const long long
     const int j = lane & (G - 1), u = lane / G;
     const int K = a.K;
     double *sP = smem;                   // LDSTAB: P-table [K][GP] {x, y} (see kHistOff)
-    double *sH = smem + kHistOff / 8;    // LDSTAB: H-table [K][GP] {h, b}
-    double *sRed = smem + (LDSTAB ? (LAY ? lay2_table_bytes(K, GP) : lds_table_bytes(K, GP)) / 8 : 0);  // [waves][G][NV] + ll scratch
+    // LDSTAB: H-table [K][GP] {h, b}; class-split tables (their H rows hold no b): the b table [K][GP] (lay2_b_off)
+    double *sH = smem + (LAY ? lay2_table_bytes(K, GP) : (size_t)kHistOff) / 8;
+    double *sRed = smem + (LDSTAB ? (LAY ? lay2_total_bytes(K, GP) : lds_table_bytes(K, GP)) / 8 : 0);  // [waves][G][NV] + ll scratch
     bool merged = false;
     if constexpr (LDSTAB && !FWD_ONLY) merged = a.merged != 0;
     const int wpb = JOIN ? kBlock / kWave : blockDim.x >> 6;  // waves of a full (sequence-group) workgroup
@@ -591,7 +599,9 @@ __device__ __forceinline__ void estep_small_body(const EArgs &a, const long long
 #pragma unroll
             for (int i = 0; i < 4; ++i) Q[i] = loadpack(i < nch ? i : nch - 1);
             double b00;  // b_j(o_0) for pi_j b_j(o_0) (:357-360)
-            if constexpr (PT) b00 = *reinterpret_cast<const double *>(pent(Q[0], 0) + HOFF + 8);  // H.b
+            if constexpr (PT && LAY)  // the b table's row of o_0: a quarter of the pack's row offset
+                b00 = sH[(sym_of(Q[0], 0) >> kLay2BPackShift) / 8 + j];
+            else if constexpr (PT) b00 = *reinterpret_cast<const double *>(pent(Q[0], 0) + HOFF + 8);  // H.b
             else b00 = *brow(Q[0], 0);
             Em E[2][kChunk];
 #pragma unroll
@@ -820,15 +830,29 @@ __device__ __forceinline__ void estep_small_body(const EArgs &a, const long long
                 // LDSTAB: this lane's table-row byte offsets of a chunk's symbols, computed once when the
                 // chunk's emission rows are read (one chunk ahead) and reused by its histogram atomics
                 // (32-bit LDS byte addresses, the table base included, so the atomics need no add)
+                // Class-split tables: HA holds the add's own address, the slot's histogram half included
+                // (lay2_add_off; the read's address must stay 16-B aligned), formed here beside the read's, off
+                // the chunk's dependent chain: one more 32-bit add per step, and the atomics' offset is 0.
+                // (Left-to-right.  Dense, when the layout is forced on, keeps the read's address in HA and adds
+                // the half's 8 bytes at the atomic: the address pair held a chunk ahead costs it 256 VGPRs and
+                // scratch, against 249 and none this way.)
                 unsigned HA[2][kChunk];
+                constexpr bool HAA = LAY && PT;  // HA holds the add's own address
+                const unsigned pja = lds_addr(pj) + (HAA ? (unsigned)lay2_add_off(GP, u) : 0u);
+                const unsigned hpar = (LAY && !HAA) ? 8u * (unsigned)(u & 1) : 0u;
+                constexpr int AOFF = HAA ? 0 : HOFF;  // immediate offset of the histogram add
                 auto ldrows = [&](Em (&bv)[kChunk], double (&bu)[kChunk], unsigned (&ha)[kChunk], const uint4 &p) {
 #pragma unroll
                     for (int k = 0; k < kChunk; ++k) {
-                        if constexpr (LDSTAB) ha[k] = lds_addr(pj) + (unsigned)sym_of(p, k);
+                        unsigned ra = 0;  // the emission read's address
+                        if constexpr (LDSTAB) {
+                            ra = lds_addr(pj) + (unsigned)sym_of(p, k);
+                            ha[k] = HAA ? pja + (unsigned)sym_of(p, k) : ra;
+                        }
                         if constexpr (PT) {
-                            bv[k] = *reinterpret_cast<const double2 *>(lds_ptr(ha[k]));
+                            bv[k] = *reinterpret_cast<const double2 *>(lds_ptr(ra));
                         } else {
-                            const double *r = LDSTAB ? reinterpret_cast<const double *>(lds_ptr(ha[k])) : brow(p, k);
+                            const double *r = LDSTAB ? reinterpret_cast<const double *>(lds_ptr(ra)) : brow(p, k);
                             bv[k] = r[0];
                             if constexpr (LR) bu[k] = r[1];  // b_{j+1}(o): the neighbour's emission
                         }
@@ -973,7 +997,7 @@ __device__ __forceinline__ void estep_small_body(const EArgs &a, const long long
                         // columns), so the compiler's lgkmcnt bookkeeping stays exact
 #pragma unroll
                         for (int k = 0; k < kChunk; ++k)  // :474-485
-                            atomicAdd(reinterpret_cast<double *>(lds_ptr(hac[k]) + HOFF), gk[k]);  // H.h of o_t
+                            atomicAdd(reinterpret_cast<double *>(lds_ptr(hac[k] + hpar) + AOFF), gk[k]);  // H.h of o_t
                     } else if (N == G || jv) {
 #pragma unroll
                         for (int k = 0; k < kChunk; ++k)
@@ -1090,9 +1114,11 @@ __device__ __forceinline__ void estep_small_body(const EArgs &a, const long long
             const int k = idx / G, jj = idx - k * G;
             if (jj >= N) continue;
             double x;
-            if constexpr (LAY) {  // the two classes' histograms of (k, jj)
+            if constexpr (LAY) {  // the four pieces of (k, jj): two classes x two slot parities
                 const char *h = reinterpret_cast<const char *>(smem) + lay2_p_off(GP, 0, k, jj) + HOFF;
-                x = *reinterpret_cast<const double *>(h) + *reinterpret_cast<const double *>(h + lay2_class_off(GP));
+                const double2 h0 = *reinterpret_cast<const double2 *>(h);
+                const double2 h1 = *reinterpret_cast<const double2 *>(h + lay2_class_off(GP));
+                x = (h0.x + h0.y) + (h1.x + h1.y);
             } else {
                 x = sH[((size_t)k * GP + jj) * 2];
             }

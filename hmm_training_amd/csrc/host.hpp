@@ -249,11 +249,12 @@ struct hmmbw_ctx {
     // LDS doubles of the small kernels' tables
     size_t lds_table_doubles() const { return lds_tables() ? lds_table_bytes(K, G) / sizeof(double) : 0; }
     // the class-split tables (lds_layout.hpp, lay2_p_off) can serve this context's joined launches: G = 8,
-    // the rows of one class within 64 KiB (uint16 packs); both classes then fit the CU's 160 KiB with the scratch
+    // the rows of one class within 64 KiB (uint16 packs); both classes and the b table then fit the CU's 160 KiB
+    // with the scratch and the kernel's static LDS (lay2_lds_fit)
     bool split_tables() const {
-        return sw.lds_layout != 0 && !wide && !det && G == 8 && lds_tables() && lay2_tables_fit(K, G);
+        return sw.lds_layout != 0 && !wide && !det && G == 8 && lds_tables() && lay2_lds_fit(K, G);
     }
-    size_t split_table_doubles() const { return lay2_table_bytes(K, G) / sizeof(double); }
+    size_t split_table_doubles() const { return lay2_total_bytes(K, G) / sizeof(double); }
     bool can_merge() const { return merge_mstep && lds_tables() && copy_len() <= kMergedMaxStats && nwaves > 0; }
     // statistics copies in the fused all-reduce buffer: the wide path's B numerator is written once (by
     // k_bnum_gather, into copy 0), and its tiles finish at different times, so its atomics need no

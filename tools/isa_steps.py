@@ -18,7 +18,7 @@ def main():
     import bench
     import isa_loops
     from hmm_training_amd import build as B
-    out = sys.argv[1] if len(sys.argv) > 1 else os.path.join(ROOT, "profiles", "r7", "isa_lr_steps.json")
+    out = sys.argv[1] if len(sys.argv) > 1 else os.path.join(ROOT, "profiles", "r10", "isa_lr_steps.json")
     with tempfile.TemporaryDirectory() as td:
         s = os.path.join(td, "n8.s")
         cmd = [B.HIPCC, *[f for f in B.FLAGS if f not in ("-fPIC",)], "-DHMMBW_INST_N=8", "--cuda-device-only", "-S",

@@ -9,7 +9,9 @@ addresses on one bank.
 
 Layouts (hmmbw_device.hpp): "rows", two [K][GP] tables of 16-B entries (P, then H kHistOff bytes on);
 "split", the joined map's class-split tables: slot u uses class (u >> 1) & 1, each class K rows of
-[P row | H row] (2 GP 16 bytes), class 1's region 65,536 + GP 16 bytes after class 0's (lay2_p_off).
+[P row | H row] (2 GP 16 bytes), class 1's region 65,536 + GP 16 bytes after class 0's (lay2_p_off), as the
+model stood with H entries {h, b}; "parity", what the kernel runs: the same tables with H entries
+{h_even, h_odd}, slot u adding into half u & 1 (lay2_add_off), and b in a compact table after them.
 Symbols: "uniform" random, "equal" (every slot the same symbol) or "two" (drawn from {0, K - 1}).
 
     python tools/lds_banks.py [G] [K]
@@ -57,9 +59,30 @@ def split_pack(GP, o):
     return o * split_row_bytes(GP)
 
 
+def parity_add_off(GP, u):
+    """Byte distance from slot u's P entry to the 8-B histogram field it adds to: mirrors lay2_add_off.
+    The H entry of "parity" is {h_even, h_odd}; slot u adds into half u & 1."""
+    return split_hist_off(GP) + 8 * (u & 1)
+
+
+def parity_b_off(K, GP, o, j):
+    """Byte offset of b_j(o) in the compact table after the class tables: mirrors lay2_b_off."""
+    return split_table_bytes(K, GP) + (o * GP + j) * 8
+
+
+def parity_total_bytes(K, GP):
+    """Class tables + b table: mirrors lay2_total_bytes."""
+    return split_table_bytes(K, GP) + K * GP * 8
+
+
+def parity_add_addr(GP, u, o, j):
+    """Byte address (from the tables' base) of the histogram add of state j of slot u on symbol o."""
+    return split_p_off(GP, split_class(u), o, j) + parity_add_off(GP, u)
+
+
 def p_entry(layout, GP, u, o, j):
     """16-B entry index of the P entry that state j of slot u reads for symbol o."""
-    if layout == "split":
+    if layout in ("split", "parity"):
         return split_p_off(GP, split_class(u), o, j) // 16
     return o * GP + j
 
@@ -69,6 +92,13 @@ def h_entry(layout, GP, K, u, o, j):
     if layout == "split":
         return (split_p_off(GP, split_class(u), o, j) + split_hist_off(GP)) // 16
     return o * GP + j
+
+
+def h_word(layout, GP, K, u, o, j):
+    """First 4-B word of the 8-B field the histogram add touches: the entry's first half, or ("parity") slot u's half."""
+    if layout == "parity":
+        return parity_add_addr(GP, u, o, j) // 4
+    return h_entry(layout, GP, K, u, o, j) * 4
 
 
 def draw(K, n, rng, symbols):
@@ -99,7 +129,7 @@ def add_cycles(G, GP, K, rng, trials=4000, layout="rows", symbols="uniform"):
         for gi in range(4):
             banks = {}
             for l in range(16 * gi, 16 * gi + 16):
-                w = h_entry(layout, GP, K, l // G, int(o[l // G]), l % G) * 4
+                w = h_word(layout, GP, K, l // G, int(o[l // G]), l % G)
                 for b in (w, w + 1):
                     banks.setdefault(b % 32, set()).add(b)
             tot += max(len(v) for v in banks.values())
@@ -110,10 +140,10 @@ if __name__ == "__main__":
     G = int(sys.argv[1]) if len(sys.argv) > 1 else 8
     K = int(sys.argv[2]) if len(sys.argv) > 2 else 256
     rng = np.random.default_rng(0)
-    for layout, pad in (("rows", 0), ("rows", 1), ("split", 0)):
+    for layout, pad in (("rows", 0), ("rows", 1), ("split", 0), ("parity", 0)):
         GP = G + pad
         for symbols in ("uniform", "equal", "two"):
-            print(f"G={G} GP={GP} {layout:5s} {symbols:7s}: "
+            print(f"G={G} GP={GP} {layout:6s} {symbols:7s}: "
                   f"ds_read_b128 {read_cycles(G, GP, K, rng, 2000, layout, symbols):.2f} cycles/group, "
                   f"ds_add_f64 {add_cycles(G, GP, K, rng, 2000, layout, symbols):.2f} cycles/group "
                   f"(1.00 = conflict-free)")
