@@ -40,7 +40,7 @@ EXPORTED = (
     "hmmbw_comm_probe", "hmmbw_comm_info", "hmmbw_comm_payload", "hmmbw_iterate_begin", "hmmbw_iterate_end",
     "hmmbw_cache_trim", "hmmbw_timing_split", "hmmbw_peer_region", "hmmbw_peer_ipc_handle", "hmmbw_peer_open",
     "hmmbw_peer_attach", "hmmbw_allreduce_kind", "hmmbw_status_live_wait", "hmmbw_get_option", "hmmbw_viterbi",
-    "hmmbw_posterior", "hmmbw_lbg_train",
+    "hmmbw_posterior", "hmmbw_lbg_train", "hmmbw_wordnet_decode",
 )
 ABI_VERSION = 5
 OPT_SAFE_SCALING = 1
@@ -65,6 +65,8 @@ INFO_JOINED = 108
 INFO_SPLIT_EXTRA = 109
 INFO_LDS_LAYOUT = 113
 ALLREDUCE = {"rccl": 0, "peer": 1}
+WORDNET_END_FINAL = 1
+WORDNET_DENSE = 2
 
 
 class HMMBWError(RuntimeError):
@@ -126,6 +128,9 @@ def _declare(lib):
         "hmmbw_viterbi": (ctypes.c_int, [c_ctx, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64]),
         "hmmbw_posterior": (ctypes.c_int, [c_ctx, ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p, ctypes.c_int64,
                                            ctypes.c_void_p]),
+        "hmmbw_wordnet_decode": (ctypes.c_int, [c_ctx, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
+                                                ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p,
+                                                ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64]),
         "hmmbw_timing": (ctypes.c_int, [c_ctx, ctypes.c_int, P(ctypes.c_double), P(ctypes.c_int64)]),
         "hmmbw_timing_split": (ctypes.c_int, [c_ctx, P(ctypes.c_double), P(ctypes.c_int64)]),
         "hmmbw_peer_region": (ctypes.c_int, [c_ctx, P(ctypes.c_void_p), P(ctypes.c_int64)]),

@@ -259,6 +259,7 @@ static void free_obs(hmmbw_ctx *c) {
     dfree(c->d_gam); dfree(c->d_bptr); dfree(c->d_brows); dfree(c->d_part); dfree(c->d_wq);
     viterbi_free(c);
     posterior_free(c);
+    wordnet_free(c);
     c->wq_grid = 0;
     c->has_obs = false;
 }

@@ -2,7 +2,7 @@
 // allocator's interface, the timing event pool, the launch plan, the context and the few helpers that
 // cross units.  Owners: alloc.hip (block cache, ledger), peer.hip (peer all-reduce), comm.hip (RCCL),
 // group.hip (grouped launches), viterbi.hip (hmmbw_viterbi and its kernels), posterior.hip (hmmbw_posterior and
-// its kernels), hmmbw.hip (everything else, and the
+// its kernels), wordnet.hip (hmmbw_wordnet_decode and its kernels), hmmbw.hip (everything else, and the
 // definitions of the helpers below).
 // The observation layout and the launch map hmmbw.hip plans are obs_plan.hpp's: pure, shared with the
 // kernels, tested without a GPU (tests/test_obs_plan.py).
@@ -24,6 +24,7 @@
 #include "lds_layout.hpp"
 #include "obs_plan.hpp"
 #include "viterbi_plan.hpp"
+#include "wordnet_plan.hpp"
 
 namespace hmmbw {
 
@@ -181,6 +182,18 @@ struct hmmbw_ctx {
         double *d_scratch = nullptr;  // [total][N]: the alpha_hat -> gamma workspace of calls without gamma_dev
         int32_t *d_path = nullptr;    // with paths only: caller CSR order
     } post;
+    // hmmbw_wordnet_decode (wordnet.hip): it shares the decoder's slot_out and device logp; its own buffers are
+    // allocated on first use (the back-pointers on the first decode with paths) and freed with the observations
+    struct Wordnet {
+        int GW = 0;                        // the group width d_psi_off and d_bp were planned for (0: none)
+        long long rows = 0, nvw = 0;       // back-pointer rows of all decoding waves | decoding waves
+        long long *d_psi_off = nullptr;    // decoding wave -> its first back-pointer row
+        double *d_in = nullptr, *d_tab = nullptr;  // the staged bank (linear) | the log tables (wordnet_plan.hpp)
+        size_t n_in = 0, n_tab = 0;        // their lengths in doubles
+        int32_t *d_path = nullptr;         // with paths only: caller CSR order
+        unsigned char *d_start = nullptr;  // with paths only: caller CSR order
+        unsigned char *d_bp = nullptr;     // with paths only: rows x kWnRowBytes
+    } wn;
     // native RCCL communicator (hmmbw_comm_init): the multi-rank hmmbw_iterate all-reduces d_ext
     ncclComm_t comm = nullptr;
     double *d_ext = nullptr;      // non-fused multi-rank paths: the packed statistics to all-reduce
@@ -296,6 +309,9 @@ int viterbi_plan_ready(hmmbw_ctx *c);  // c->vit.plan, d_slot_out and d_logp of 
 
 // posterior.hip
 void posterior_free(hmmbw_ctx *c);  // hmmbw_posterior's buffers; callers synchronise the context first
+
+// wordnet.hip
+void wordnet_free(hmmbw_ctx *c);  // hmmbw_wordnet_decode's buffers; callers synchronise the context first
 
 // peer.hip
 std::string peer_off_msg(const hmmbw_ctx *c);

@@ -49,9 +49,12 @@ struct ViterbiPlan {
 // slot_len / slot_seq: the observation layout's slot arrays (obs_plan.hpp: 0 / -1 in padding slots); R sequences.
 // The output offsets are the prefix sum of the lengths in caller order; a decoding wave holds spw consecutive
 // slots and as many back-pointer rows as its longest slot has steps.
-inline ViterbiPlan plan_viterbi(const std::vector<int> &slot_len, const std::vector<int> &slot_seq, long long R, int N) {
+// plan_viterbi_group takes the lane-group width itself (8, 16, 32 or 64): the word-loop decoder's groups hold
+// words, not states (wordnet_plan.hpp).
+inline ViterbiPlan plan_viterbi_group(const std::vector<int> &slot_len, const std::vector<int> &slot_seq, long long R,
+                                      int GV) {
     ViterbiPlan P;
-    P.GV = viterbi_gv(N);
+    P.GV = GV;
     P.spw = kVitWave / P.GV;
     P.nslots = (long long)slot_len.size();
     P.nvw = (P.nslots + P.spw - 1) / P.spw;
@@ -71,6 +74,10 @@ inline ViterbiPlan plan_viterbi(const std::vector<int> &slot_len, const std::vec
         P.psi_rows += Tw;
     }
     return P;
+}
+
+inline ViterbiPlan plan_viterbi(const std::vector<int> &slot_len, const std::vector<int> &slot_seq, long long R, int N) {
+    return plan_viterbi_group(slot_len, slot_seq, R, viterbi_gv(N));
 }
 
 }  // namespace hmmbw

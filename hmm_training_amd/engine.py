@@ -27,7 +27,7 @@ import torch
 
 from ._lib import (ALLREDUCE, INFO_WIDE_WQ_ACTIVE, OPT_ALLREDUCE, OPT_DETERMINISTIC, OPT_LIVE_STATUS, OPT_MERGE_MSTEP,
                    OPT_PEER_TIMEOUT_MS, OPT_SAFE_SCALING, OPT_STAT_COPIES, OPT_WIDE_WQ, OPT_WQ_TIMEOUT_MS, TOPOLOGY,
-                   TOPOLOGY_NAME, IterRecord, Status, check, lib)
+                   TOPOLOGY_NAME, WORDNET_DENSE, WORDNET_END_FINAL, IterRecord, Status, check, lib)
 
 IterCallback = Callable[[int, float, float], None]
 
@@ -575,6 +575,44 @@ class BaumWelchEngine:
         if paths:
             split = np.split(flat[:total], self._offsets[1:-1]) if self.n_seq else []
         return g, split, logp[: self.n_seq]
+
+    def wordnet_decode(self, pi, A, B, word_init=None, word_trans=None, end_final: bool = False, dense: bool = False,
+                       paths: bool = True):
+        """Connected-word decoding of every loaded sequence through a loop of W word models of the engine's shape
+        (hmmbw_wordnet_decode): (paths, starts, logp).  pi [W, N], A [W, N, N], B [W, N, M]; word_init [W] and
+        word_trans [W, W] are non-negative weights (None: all ones).  paths: one int32 array of composite states
+        w N + j per sequence (all -1 where logp is -inf); starts: one uint8 array per sequence, 1 at the first frame
+        of every word instance; both None with paths=False (scores only).  end_final: the path ends in a last
+        state; dense: the dense within-word scan even for a left-to-right bank.  Needs observations only: the
+        engine's own parameters and training state are neither read nor changed."""
+        pi = np.ascontiguousarray(pi, dtype=np.float64)
+        if pi.ndim != 2 or pi.shape[1] != self.N:
+            raise ValueError(f"pi must be [W, {self.N}], not {pi.shape}")
+        W = pi.shape[0]
+        A = np.ascontiguousarray(A, dtype=np.float64)
+        B = np.ascontiguousarray(B, dtype=np.float64)
+        if A.shape != (W, self.N, self.N) or B.shape != (W, self.N, self.M):
+            raise ValueError(f"A must be [{W}, {self.N}, {self.N}] and B [{W}, {self.N}, {self.M}], "
+                             f"not {A.shape} and {B.shape}")
+        init = None if word_init is None else np.ascontiguousarray(word_init, dtype=np.float64)
+        trans = None if word_trans is None else np.ascontiguousarray(word_trans, dtype=np.float64)
+        if (init is not None and init.shape != (W,)) or (trans is not None and trans.shape != (W, W)):
+            raise ValueError(f"word_init must be [{W}] and word_trans [{W}, {W}]")
+        flags = (WORDNET_END_FINAL if end_final else 0) | (WORDNET_DENSE if dense else 0)
+        logp = np.zeros(max(self.n_seq, 1))
+        total = getattr(self, "n_symbols_total", 0)
+        flat = np.zeros(max(total, 1), dtype=np.int32) if paths else None
+        first = np.zeros(max(total, 1), dtype=np.uint8) if paths else None
+        check(self._lib.hmmbw_wordnet_decode(
+            self._ctx, W, pi.ctypes.data, A.ctypes.data, B.ctypes.data, None if init is None else init.ctypes.data,
+            None if trans is None else trans.ctypes.data, flags, logp.ctypes.data,
+            flat.ctypes.data if paths else None, first.ctypes.data if paths else None, total))
+        if not paths:
+            return None, None, logp[: self.n_seq]
+        if not self.n_seq:
+            return [], [], logp[:0]
+        cut = self._offsets[1:-1]
+        return np.split(flat[:total], cut), np.split(first[:total], cut), logp[: self.n_seq]
 
     def timing(self, enable: int = -1) -> Tuple[float, int]:
         """(accumulated E-step ms, timed launches) of hmmbw_timing; enable >= 0 also resets and sets the

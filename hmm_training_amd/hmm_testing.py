@@ -84,6 +84,42 @@ def posterior_decode(observations: Sequence[np.ndarray], hmm: HMMTrained,
         return np.split(gamma.cpu().numpy(), eng._offsets[1:-1]), paths, logp
 
 
+def segments_from_path(path: np.ndarray, starts: np.ndarray, N: int, words: Sequence) -> List[Tuple[object, int, int]]:
+    """[(word, start_frame, end_frame_exclusive), ...] of one decoded sequence: a segment opens at every frame whose
+    start flag is set and carries the word of its composite state (path[t] // N).  A repeated word gives two
+    segments, a held word one.  A sequence without a path (all -1) has no segments."""
+    path, starts = np.asarray(path), np.asarray(starts)
+    if path.size == 0 or path[0] < 0:
+        return []
+    first = np.flatnonzero(starts)
+    ends = np.append(first[1:], path.size)
+    return [(words[int(path[s]) // N], int(s), int(e)) for s, e in zip(first, ends)]
+
+
+def decode_words(observations: Sequence[np.ndarray], models: Sequence[HMMTrained], word_init=None, word_trans=None,
+                 end_final: bool = True, device=None) -> Tuple[List[List[Tuple[object, int, int]]], np.ndarray]:
+    """(segments, logp): which words were spoken, and where, in every recording: the best path through a loop of the
+    word models, all sequences in one launch (BaumWelchEngine.wordnet_decode).  segments[r] lists (word,
+    start_frame, end_frame_exclusive) with the models' .word names.  word_init [W] and word_trans [W, W] are
+    non-negative weights (a grammar and a word-insertion penalty; None: all ones).  The models must share one shape."""
+    if len(observations) == 0:
+        return [], np.zeros(0)
+    if len(models) == 0:
+        raise ValueError("no word models")
+    N, M = int(models[0].states), int(np.asarray(models[0].B).shape[1])
+    for hmm in models:
+        if int(hmm.states) != N or np.asarray(hmm.B).shape != (N, M) or np.asarray(hmm.A).shape != (N, N):
+            raise ValueError("connected-word decoding needs word models of one shape (N states, M symbols)")
+    pi = np.stack([np.asarray(h.Pi, dtype=np.float64).reshape(N) for h in models])
+    A = np.stack([np.asarray(h.A, dtype=np.float64) for h in models])
+    B = np.stack([np.asarray(h.B, dtype=np.float64) for h in models])
+    words = [h.word for h in models]
+    with BaumWelchEngine(N, M, device=device) as eng:
+        eng.set_observations(observations)
+        paths, starts, logp = eng.wordnet_decode(pi, A, B, word_init, word_trans, end_final=end_final)
+    return [segments_from_path(p, s, N, words) for p, s in zip(paths, starts)], logp
+
+
 def calculate_log_likelihood(recording_observations: np.ndarray, hmm: HMMTrained) -> float:
     """log P(O | lambda) of one sequence under one linear-domain model (hmm_testing.py:49-104)."""
     return float(score_matrix([np.asarray(recording_observations)], [hmm])[0, 0])

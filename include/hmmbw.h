@@ -41,7 +41,8 @@ extern "C" {
                                  hmmbw_viterbi is a new entry point of version 5: an older library lacks the
                                  symbol; hmmbw_posterior is a new entry point of version 5: an older library
                                  lacks the symbol; hmmbw_lbg_train is a new entry point of version 5: an older
-                                 library lacks the symbol) */
+                                 library lacks the symbol; hmmbw_wordnet_decode is a new entry point of version
+                                 5: an older library lacks the symbol) */
 
 #define HMMBW_OK 0
 #define HMMBW_E_INVALID (-1)        /* bad argument (shape, range, null pointer)             */
@@ -269,6 +270,38 @@ int hmmbw_viterbi(hmmbw_ctx *ctx, double *logp_out, int32_t *path_out, int64_t p
  * Leaves the log-likelihoods of hmmbw_get_loglik, the statistics and the training state as they were. */
 int hmmbw_posterior(hmmbw_ctx *ctx, double *gamma_dev, int64_t gamma_len,
                     int32_t *path_out, int64_t path_len, double *logp_out);
+
+/* SYNC. Connected-word decoding of the loaded sequences: the Viterbi path through a loop of n_words word models of
+ * the context's shape (N states, M symbols), log domain, fp64.  The bank is given with the call, HOST arrays of
+ * linear doubles: pi [W][N], A [W][N][N], B [W][N][M], word weights word_init [W] (NULL: all ones) and
+ * word-transition weights word_trans [W][W] (NULL: all ones), any non-negative numbers, not necessarily
+ * stochastic: 0 forbids a transition, a common factor is a word-insertion penalty.  Composite state (w, j) has
+ * index w N + j:
+ *   delta_0(w,j) = (log init_w + log pi_w[j]) + log b_w,j(o_0)
+ *   inner_t(w,j) = max_i delta_{t-1}(w,i) + log a_w[i][j]       the SMALLEST i on ties (strict '>' scan from 0)
+ *   E_t(w)       = max_v delta_{t-1}(v,N-1) + log G[v][w]       the smallest v on ties
+ *   entry_t(w,j) = E_t(w) + log pi_w[j]
+ *   delta_t(w,j) = (entry_t > inner_t ? entry_t : inner_t) + log b_w,j(o_t)      the within-word arc wins ties
+ * A word is left only from its last state N - 1 and may be re-entered at any state j, weighted by pi_w[j].
+ * End state: the smallest composite index attaining max delta_{T-1}; with HMMBW_WORDNET_END_FINAL only the
+ * states (w, N - 1) compete.  HMMBW_WORDNET_DENSE forces the dense within-word scan even if every A is
+ * left-to-right (a_ij = 0 unless j = i or j = i + 1, detected from the bank).
+ * logp_out[r] (R doubles, caller order): the best path's log-probability, -inf if no path has positive
+ * probability.  path_out (may be NULL: scores only, no back-pointers are stored): int32, caller CSR order,
+ * path_out[offsets[r] + t] = w N + j.  start_out (may be NULL; only together with path_out): uint8, caller CSR
+ * order, 1 iff frame t is the first frame of a word instance (t = 0, or the step into t took the entry arc).
+ * A sequence whose logp is -inf has path -1 and start 0 throughout.  No NaN anywhere.
+ * path_len must equal the total number of loaded symbols (HMMBW_E_INVALID otherwise), as in hmmbw_viterbi.
+ * HMMBW_E_INVALID: n_words < 1, a NULL pi, A, B or logp_out, start_out without path_out, a negative, infinite
+ * or NaN weight or bank parameter.  HMMBW_E_UNSUPPORTED: n_words > 64, or a context of N > 8.
+ * HMMBW_E_STATE: no observations loaded, or an iteration is open (hmmbw_iterate_begin).
+ * Needs loaded observations only: it neither reads nor changes the context's parameters, statistics,
+ * hmmbw_get_loglik values or training state.  A multi-rank context decodes its own shard, no collective. */
+#define HMMBW_WORDNET_END_FINAL 1
+#define HMMBW_WORDNET_DENSE     2   /* force the dense within-word scan even if every A is left-to-right */
+int hmmbw_wordnet_decode(hmmbw_ctx *ctx, int n_words, const double *pi, const double *A, const double *B,
+                         const double *word_init, const double *word_trans, int flags,
+                         double *logp_out, int32_t *path_out, uint8_t *start_out, int64_t path_len);
 
 /* Engine knobs.  HMMBW_OPT_SAFE_SCALING = 1 forces the per-step power-of-two normalisation of the
  * forward recursion (default 0: lagged normalisation, automatic per-wave fallback to the per-step
