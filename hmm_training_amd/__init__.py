@@ -8,12 +8,13 @@ from .hmm_classes import DataStorageHMM, HMMTrained  # noqa: F401
 __all__ = ["HMMTrained", "DataStorageHMM", "hmm_training", "training_with_save", "get_observations",
            "calculate_log_likelihood", "viterbi_decode", "posterior_decode", "decode_words", "BaumWelchEngine",
            "lbg_train",
-           "createCodeVector", "save_centroids"]
+           "createCodeVector", "save_centroids", "train_connected"]
 
 
 def __getattr__(name):
     # the engine-backed entry points load libhmmbw.so (and torch) lazily
-    if name in ("hmm_training", "training_with_save", "get_observations", "safe_log", "safe_exp", "log_sum_exp"):
+    if name in ("hmm_training", "training_with_save", "get_observations", "safe_log", "safe_exp", "log_sum_exp",
+                "train_connected"):
         from . import hmm_training as _ht
         return getattr(_ht, name)
     if name in ("calculate_log_likelihood", "score_matrix", "test_hmm", "viterbi_decode", "posterior_decode",

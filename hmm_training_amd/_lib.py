@@ -40,7 +40,7 @@ EXPORTED = (
     "hmmbw_comm_probe", "hmmbw_comm_info", "hmmbw_comm_payload", "hmmbw_iterate_begin", "hmmbw_iterate_end",
     "hmmbw_cache_trim", "hmmbw_timing_split", "hmmbw_peer_region", "hmmbw_peer_ipc_handle", "hmmbw_peer_open",
     "hmmbw_peer_attach", "hmmbw_allreduce_kind", "hmmbw_status_live_wait", "hmmbw_get_option", "hmmbw_viterbi",
-    "hmmbw_posterior", "hmmbw_lbg_train", "hmmbw_wordnet_decode",
+    "hmmbw_posterior", "hmmbw_lbg_train", "hmmbw_wordnet_decode", "hmmbw_embedded_train",
 )
 ABI_VERSION = 5
 OPT_SAFE_SCALING = 1
@@ -67,6 +67,8 @@ INFO_LDS_LAYOUT = 113
 ALLREDUCE = {"rccl": 0, "peer": 1}
 WORDNET_END_FINAL = 1
 WORDNET_DENSE = 2
+EMBED_END_FINAL = 1
+EMBED_DENSE = 2
 
 
 class HMMBWError(RuntimeError):
@@ -131,6 +133,10 @@ def _declare(lib):
         "hmmbw_wordnet_decode": (ctypes.c_int, [c_ctx, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
                                                 ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p,
                                                 ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64]),
+        "hmmbw_embedded_train": (ctypes.c_int, [c_ctx, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
+                                                ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64, ctypes.c_int,
+                                                ctypes.c_double, ctypes.c_int64, ctypes.c_int, ctypes.c_void_p,
+                                                ctypes.c_int64, P(ctypes.c_int64), ctypes.c_void_p]),
         "hmmbw_timing": (ctypes.c_int, [c_ctx, ctypes.c_int, P(ctypes.c_double), P(ctypes.c_int64)]),
         "hmmbw_timing_split": (ctypes.c_int, [c_ctx, P(ctypes.c_double), P(ctypes.c_int64)]),
         "hmmbw_peer_region": (ctypes.c_int, [c_ctx, P(ctypes.c_void_p), P(ctypes.c_int64)]),

@@ -2,8 +2,8 @@
 // allocator's interface, the timing event pool, the launch plan, the context and the few helpers that
 // cross units.  Owners: alloc.hip (block cache, ledger), peer.hip (peer all-reduce), comm.hip (RCCL),
 // group.hip (grouped launches), viterbi.hip (hmmbw_viterbi and its kernels), posterior.hip (hmmbw_posterior and
-// its kernels), wordnet.hip (hmmbw_wordnet_decode and its kernels), hmmbw.hip (everything else, and the
-// definitions of the helpers below).
+// its kernels), wordnet.hip (hmmbw_wordnet_decode and its kernels), embedded.hip (hmmbw_embedded_train and its
+// kernels; it keeps nothing in the context), hmmbw.hip (everything else, and the definitions of the helpers below).
 // The observation layout and the launch map hmmbw.hip plans are obs_plan.hpp's: pure, shared with the
 // kernels, tested without a GPU (tests/test_obs_plan.py).
 #pragma once

@@ -27,7 +27,8 @@ import torch
 
 from ._lib import (ALLREDUCE, INFO_WIDE_WQ_ACTIVE, OPT_ALLREDUCE, OPT_DETERMINISTIC, OPT_LIVE_STATUS, OPT_MERGE_MSTEP,
                    OPT_PEER_TIMEOUT_MS, OPT_SAFE_SCALING, OPT_STAT_COPIES, OPT_WIDE_WQ, OPT_WQ_TIMEOUT_MS, TOPOLOGY,
-                   TOPOLOGY_NAME, WORDNET_DENSE, WORDNET_END_FINAL, IterRecord, Status, check, lib)
+                   TOPOLOGY_NAME, WORDNET_DENSE, WORDNET_END_FINAL, EMBED_DENSE, EMBED_END_FINAL, IterRecord, Status,
+                   check, lib)
 
 IterCallback = Callable[[int, float, float], None]
 
@@ -613,6 +614,44 @@ class BaumWelchEngine:
             return [], [], logp[:0]
         cut = self._offsets[1:-1]
         return np.split(flat[:total], cut), np.split(first[:total], cut), logp[: self.n_seq]
+
+    def embedded_train(self, pi, A, B, transcripts, epsilon: float = 1e-6, max_iterations: int = 100,
+                       end_final: bool = False, dense: bool = False, normalise: bool = True):
+        """Embedded Baum-Welch training of a bank of W word models of the engine's shape from the loaded sequences
+        and their transcripts (hmmbw_embedded_train): (pi, A, B, records, logp).  pi [W, N], A [W, N, N],
+        B [W, N, M] are the start bank (the arguments are not changed); transcripts[r] lists the word ids spoken in
+        sequence r, in order.  records: the (L, diff) of every iteration made; logp: log P_r of the last E-step
+        (-inf where no path explains the sequence).  end_final: an utterance ends in the last state of its last
+        word; dense: the dense within-word products even for a left-to-right bank; normalise=False returns the
+        working parameters, from which a second call continues exactly.  Needs observations only: the engine's own
+        parameters and training state are neither read nor changed."""
+        pi = np.array(pi, dtype=np.float64, order="C")
+        if pi.ndim != 2 or pi.shape[1] != self.N:
+            raise ValueError(f"pi must be [W, {self.N}], not {pi.shape}")
+        W = pi.shape[0]
+        A = np.array(A, dtype=np.float64, order="C")
+        B = np.array(B, dtype=np.float64, order="C")
+        if A.shape != (W, self.N, self.N) or B.shape != (W, self.N, self.M):
+            raise ValueError(f"A must be [{W}, {self.N}, {self.N}] and B [{W}, {self.N}, {self.M}], "
+                             f"not {A.shape} and {B.shape}")
+        if len(transcripts) != self.n_seq:
+            raise ValueError(f"{len(transcripts)} transcripts for {self.n_seq} loaded sequences")
+        off = np.zeros(len(transcripts) + 1, dtype=np.int64)
+        np.cumsum([len(t) for t in transcripts], out=off[1:])
+        ids = np.zeros(max(int(off[-1]), 1), dtype=np.int32)
+        if off[-1]:
+            ids[: off[-1]] = np.concatenate([np.asarray(t, dtype=np.int64).reshape(-1) for t in transcripts])
+        max_iterations = int(max_iterations)
+        recs = (IterRecord * max(max_iterations, 1))()
+        n = ctypes.c_int64()
+        logp = np.zeros(max(self.n_seq, 1))
+        flags = (EMBED_END_FINAL if end_final else 0) | (EMBED_DENSE if dense else 0)
+        check(self._lib.hmmbw_embedded_train(
+            self._ctx, W, pi.ctypes.data, A.ctypes.data, B.ctypes.data, off.ctypes.data, ids.ctypes.data, self.n_seq,
+            flags, float(epsilon), max_iterations, int(normalise), ctypes.cast(recs, ctypes.c_void_p),
+            max(max_iterations, 1), ctypes.byref(n), logp.ctypes.data))
+        records = [(recs[i].log_likelihood, recs[i].diff) for i in range(n.value)]
+        return pi, A, B, records, logp[: self.n_seq]
 
     def timing(self, enable: int = -1) -> Tuple[float, int]:
         """(accumulated E-step ms, timed launches) of hmmbw_timing; enable >= 0 also resets and sets the

@@ -336,6 +336,41 @@ def hmm_training_group(observation_sets: Sequence[List[np.ndarray]], N: int = 4,
     return results
 
 
+def train_connected(observations: Sequence[np.ndarray], transcripts: Sequence[Sequence], models: Sequence[HMMTrained],
+                    epsilon: float = 1e-6, max_iterations: int = 100, end_final: bool = True, *,
+                    device: Optional[int] = None) -> Tuple[List[HMMTrained], List[Tuple[float, float]]]:
+    """Embedded re-estimation of word models from connected speech (BaumWelchEngine.embedded_train): recording r
+    was spoken as the words transcripts[r], a list of the models' .word names, with no word boundaries given.
+    Returns (the re-estimated models, in the order given, and the (L, diff) record of every iteration).  A word no
+    transcript names comes back unchanged.  end_final: every recording ends in the last state of its last word, as
+    decode_words assumes by default.  The models must share one shape."""
+    if len(models) == 0:
+        raise ValueError("no word models")
+    N, M = int(models[0].states), int(np.asarray(models[0].B).shape[1])
+    for hmm in models:
+        if int(hmm.states) != N or np.asarray(hmm.B).shape != (N, M) or np.asarray(hmm.A).shape != (N, N):
+            raise ValueError("embedded training needs word models of one shape (N states, M symbols)")
+    if len(transcripts) != len(observations):
+        raise ValueError(f"{len(transcripts)} transcripts for {len(observations)} recordings")
+    index = {h.word: w for w, h in enumerate(models)}
+    ids = []
+    for r, words in enumerate(transcripts):
+        for name in words:
+            if name not in index:
+                raise ValueError(f"transcript {r} names the word {name!r}, which no model carries")
+        ids.append([index[name] for name in words])
+    if len(observations) == 0:
+        return list(models), []
+    pi = np.stack([np.asarray(h.Pi, dtype=np.float64).reshape(N) for h in models])
+    A = np.stack([np.asarray(h.A, dtype=np.float64) for h in models])
+    B = np.stack([np.asarray(h.B, dtype=np.float64) for h in models])
+    with BaumWelchEngine(N, M, device=device) as eng:
+        eng.set_observations(list(observations))
+        pi, A, B, records, _ = eng.embedded_train(pi, A, B, ids, epsilon=epsilon, max_iterations=max_iterations,
+                                                  end_final=end_final)
+    return [HMMTrained(states=N, symbols=M, A=A[w], B=B[w], Pi=pi[w], word=h.word) for w, h in enumerate(models)], records
+
+
 def training_with_save(word_recordings, centroids, word_name: str, max_iterations=100, show_progress=True,
                        load_initial_params=False, *, n_states: int = 4, base_dir: Optional[str] = None) -> HMMTrained:
     """VQ -> hmm_training(N=4) -> HMMTrained -> save JSON (hmm_training.py:215-247)."""

@@ -42,7 +42,8 @@ extern "C" {
                                  symbol; hmmbw_posterior is a new entry point of version 5: an older library
                                  lacks the symbol; hmmbw_lbg_train is a new entry point of version 5: an older
                                  library lacks the symbol; hmmbw_wordnet_decode is a new entry point of version
-                                 5: an older library lacks the symbol) */
+                                 5: an older library lacks the symbol; hmmbw_embedded_train is a new entry point
+                                 of version 5: an older library lacks the symbol) */
 
 #define HMMBW_OK 0
 #define HMMBW_E_INVALID (-1)        /* bad argument (shape, range, null pointer)             */
@@ -302,6 +303,55 @@ int hmmbw_posterior(hmmbw_ctx *ctx, double *gamma_dev, int64_t gamma_len,
 int hmmbw_wordnet_decode(hmmbw_ctx *ctx, int n_words, const double *pi, const double *A, const double *B,
                          const double *word_init, const double *word_trans, int flags,
                          double *logp_out, int32_t *path_out, uint8_t *start_out, int64_t path_len);
+
+/* SYNC. Embedded training: Baum-Welch re-estimation of a bank of n_words word models of the context's shape (N
+ * states, M symbols) from the loaded sequences and their transcripts, the training counterpart of
+ * hmmbw_wordnet_decode.  Utterance r was spoken as the words word_ids[word_offsets[r] .. word_offsets[r+1]) (CSR,
+ * caller order; a word may occur several times, immediate repeats included); where each word lies is not given.
+ * The word models are chained along the transcript, composite state (l, j) for position l and state j:
+ *   initial weight  pi_{w_0}[j] on (0, j), 0 elsewhere
+ *   within-word arc (l,i) -> (l,j)       of weight a_{w_l}[i][j]
+ *   entry arc       (l,N-1) -> (l+1,j)   of weight pi_{w_{l+1}}[j]   (the decoder's entry arc, all word-transition
+ *                                        weights 1; it does not share a row sum with the self-loop of (l, N-1))
+ *   emission        b_{w_l,j}(o_t)
+ *   end             any state of the last instance; with HMMBW_EMBED_END_FINAL only (L-1, N-1).
+ * P_r is the total weight of all complete paths.  Per iteration, over the utterances with P_r > 0, every instance
+ * of word w adds its posteriors to w's sums: entry[w][j] (gamma_0(0,j) for an instance at l = 0, the entry arcs
+ * into (l, j) otherwise: 1 per instance in all), xi[w][i][j] (the within-word arcs), a_den[w][i] = sum_j xi[w][i][j],
+ * g_all[w][j] = sum_t gamma_t(l,j), b_num[w][j][k] = sum_{t: o_t = k} gamma_t(l,j); count[w] is the number of
+ * instances of w in ALL transcripts (those of utterances with P_r = 0 too: the R of hmm_training.py:424).  Then the
+ * reference's M-step (:415-500) per word: pi = entry / count, a = xi / a_den (0 where either is 0), b = b_num / g_all
+ * (1e-20 where b_num is 0 and g_all > 0, 0 where g_all is 0); a word with count 0 keeps its parameters bit for bit,
+ * whatever `normalise` says.  Convergence as :503-514: L = LSE_r log P_r of the parameters entering the iteration,
+ * diff = |L - L_prev| (+inf on the first iteration), stop once diff < epsilon or max_iterations is reached.  All
+ * iterations run on the device (an E-step kernel, a per-word M-step kernel and a one-workgroup convergence kernel per
+ * iteration, no-ops once a device-side done is set); the host reads the state every 16 iterations.
+ * pi [W][N], A [W][N][N], B [W][N][M]: HOST, linear doubles, in: the start bank (working parameters, not necessarily
+ * normalised), out: the trained bank.  normalise = 1 applies the reference's return path (:524-541) per trained
+ * word (pi / sum pi where the sum is positive; the rows of A and B with a positive sum divided by it); normalise = 0
+ * returns the working parameters, so that a second call continues exactly where the first stopped.
+ * records (or NULL) gets the first records_cap iterations' records, *n_records (or NULL) the iterations made;
+ * logp_out (or NULL): R doubles, log P_r of the LAST E-step, -inf where P_r = 0.  No NaN anywhere.
+ * The sums are floating-point atomics: two calls agree to rounding, not bit for bit.  A composite state whose scaled
+ * forward (or backward) value is below 2^-1022 of its row's largest is treated as 0.
+ * HMMBW_EMBED_DENSE forces the dense within-word products even if every A is left-to-right.
+ * HMMBW_E_INVALID: n_words < 1, a NULL bank or transcript pointer, n_seq different from the loaded count, an empty
+ * transcript, a word id outside [0, W), a negative, infinite or NaN parameter, max_iterations < 1, epsilon negative
+ * or NaN, unknown flag bits.  HMMBW_E_UNSUPPORTED: n_words > 64, a transcript longer than 64 words, a context of
+ * N > 8, of world_size > 1 (no collective is built here) or in deterministic mode.  HMMBW_E_STATE: no observations
+ * loaded, or an iteration is open (hmmbw_iterate_begin).  HMMBW_E_HIP: the workspace (8 N x 64 bytes per step and
+ * wave of 64 / GW utterances, GW the smallest of 8, 16, 32, 64 that holds the longest transcript) could not be
+ * allocated; the message names its size.
+ * Needs loaded observations only: it neither reads nor changes the context's parameters, statistics,
+ * hmmbw_get_loglik values or training state. */
+#define HMMBW_EMBED_END_FINAL 1
+#define HMMBW_EMBED_DENSE     2   /* force the dense within-word products even if every A is left-to-right */
+int hmmbw_embedded_train(hmmbw_ctx *ctx, int n_words,
+                         double *pi, double *A, double *B,
+                         const int64_t *word_offsets, const int32_t *word_ids, int64_t n_seq,
+                         int flags, double epsilon, int64_t max_iterations, int normalise,
+                         hmmbw_iter_record *records, int64_t records_cap, int64_t *n_records,
+                         double *logp_out);
 
 /* Engine knobs.  HMMBW_OPT_SAFE_SCALING = 1 forces the per-step power-of-two normalisation of the
  * forward recursion (default 0: lagged normalisation, automatic per-wave fallback to the per-step
