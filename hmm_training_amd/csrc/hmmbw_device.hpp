@@ -435,9 +435,20 @@ __device__ __forceinline__ void estep_small_body(const EArgs &a, const long long
         const bool full = a.L.wave_full[wave] != 0;
         const int nch = (Tw + kChunk - 1) / kChunk;
         const long long symbase = a.L.wave_symoff[wave] + u * kChunk;  // pack index of this slot's chunk-0 entry
-        const uint16_t *symw = a.L.sym + symbase;
         double *ckw = a.ckpt + (FWD_ONLY ? 0 : a.L.wave_ckoff[wave] * (ZF ? kChunk : 1)) + lane;
-        uint4 *spw = a.spack + (FWD_ONLY ? 0 : a.L.wave_spoff[wave]) + u;
+        // The symbol packs and the exponent packs are both rings of U 16-byte entries per chunk, slot u's at byte
+        // 16 u of the chunk's: one 32-bit byte offset serves both, over the wave's two bases in SGPRs (the saddr
+        // form of the loads and stores), instead of a 64-bit address rebuilt from the chunk index for each.  A
+        // wave's rings span 2 U bytes per step and the ABI takes T <= 2^28, so the offsets fit 32 bits where
+        // U <= 8 (G >= 8: five states and more); the wider waves of the smaller models keep 64-bit offsets.
+        // (The checkpoints span 64 bytes per step, 512 with ZF, so they keep their 64-bit arithmetic too.)
+        constexpr unsigned kRing = U * kChunk * sizeof(uint16_t);  // a chunk's bytes in either ring
+        static_assert(kRing == U * sizeof(uint4), "the pack rings share their offsets");
+        using roff_t = typename std::conditional<(U <= 8), unsigned, unsigned long long>::type;
+        const uint16_t *symS = wave_uniform_ptr(a.L.sym + a.L.wave_symoff[wave]);
+        uint4 *spS = wave_uniform_ptr(a.spack + (FWD_ONLY ? 0 : a.L.wave_spoff[wave]));
+        const roff_t ringlane = (roff_t)u * (roff_t)sizeof(uint4);
+        auto ringoff = [&](int c) -> roff_t { return (roff_t)c * kRing + ringlane; };
         const bool jv = j < N;
         // shortest sequence of the wave: in a ragged wave the chunks every lane is still inside of run
         // unmasked.  Padding slots (T = 0; empty sequences are rejected at the ABI) do not count: their
@@ -464,7 +475,10 @@ __device__ __forceinline__ void estep_small_body(const EArgs &a, const long long
         const double pij = sPA[j];
 
         auto loadpack = [&](int c) -> uint4 {
-            return *reinterpret_cast<const uint4 *>(symw + (long long)c * U * kChunk);
+            return at_byte(reinterpret_cast<const uint4 *>(symS), ringoff(c));
+        };
+        auto exps_at = [&](int c) -> uint4 & {  // chunk c's exponent pack of this slot
+            return at_byte(spS, ringoff(c));
         };
         // This lane's P-table entry for packed entry k.  With LDS tables the packs hold the byte
         // offset of the symbol's row (o * GP * 16, precomputed on the host), else the symbol.
@@ -590,6 +604,11 @@ __device__ __forceinline__ void estep_small_body(const EArgs &a, const long long
             z = 0.0;
             C = 0;
             int pend[kChunk / kScale] = {};  // lagged: exponents to apply at the coming scale steps
+            // The sweep's own place in its streams, advanced by every chunk (the chunks run in order): the ring
+            // offset of chunk c, and where its checkpoint goes (a 64-bit pointer: see kRing)
+            roff_t roff = ringlane;
+            const roff_t rmax = ringoff(nch - 1);
+            double *ckp = ckw;
             int minM = 4096, maxM = 0;       // extreme group exponents seen (fallback trigger)
             // Symbol packs travel through a 4-deep register ring (the pack of chunk c + 4 is loaded
             // while chunk c runs) and the emissions through a 2-deep one (chunk c + 1's LDS reads are
@@ -606,9 +625,10 @@ __device__ __forceinline__ void estep_small_body(const EArgs &a, const long long
             Em E[2][kChunk];
 #pragma unroll
             for (int k = 0; k < kChunk; ++k) E[0][k] = ld_em(Q[0], k);
-            auto chunk = [&](int c, const Em (&bv)[kChunk], auto MASK_, auto FIRST_) {
+            auto chunk = [&](int c, const Em (&bv)[kChunk], auto MASK_, auto FIRST_, auto CAP_) {
                 constexpr bool MASK = decltype(MASK_)::value;
                 constexpr bool FIRST = decltype(FIRST_)::value;  // chunk 0: step 0 is pi_j b_j(o_0)
+                constexpr bool CAP = decltype(CAP_)::value;      // chunk hc may be this one: record C_h
                 const int Tend = RAG ? T : Tw;
                 int sp[kChunk];
 #pragma unroll
@@ -643,60 +663,94 @@ __device__ __forceinline__ void estep_small_body(const EArgs &a, const long long
                         z = zn;
                         C += st;
                     }
-                    if (SPLITOK && k == 0) Ch = (c == hc) ? C : Ch;  // split: C_h, h = 8 hc
+                    if (CAP && k == 0) Ch = (c == hc) ? C : Ch;  // split: C_h, h = 8 hc
                     sp[k] = st;
                     if constexpr (!FWD_ONLY) {
                         if (ZF) {  // every z_t (nontemporal measured worse, cfg3 dense 79.7-80.5 against 73.6-73.8 us)
-                            ckw[((long long)c * kChunk + k) * kWave] = z;
-                        } else if (k == 0) {
-                            ckw[(long long)c * kWave] = z;  // checkpoint z_{8c}
+                            ckp[k * kWave] = z;
+                        } else if (k == 0) {  // checkpoint z_{8c}
+                            ckp[0] = z;
                         }
                     }
                 }
-                if constexpr (!FWD_ONLY) spw[(long long)c * U] = pack_exps(sp);
+                if constexpr (!FWD_ONLY) {
+                    // lagged: the chunk's one exponent (step 8c), a dword into the head of the 16-byte slot.  Its
+                    // low half is exponent 0 as pack_exps writes it (the high half holds its sign, where safe
+                    // mode keeps exponent 1): a lagged backward reads exponent 0 alone, so a slot may change mode
+                    // from one iteration to the next
+                    uint4 &slot = at_byte(spS, roff);
+                    if constexpr (!SAFE && kScale == kChunk) reinterpret_cast<int &>(slot) = sp[0];
+                    else slot = pack_exps(sp);
+                }
+                roff += kRing;
+                ckp += (ZF ? kChunk : 1) * kWave;
             };
             // chunk c uses ring slot r = c % 4.  The steady loop runs 4 chunks per trip with no
             // branches around loads or stores, so the compiler's s_waitcnt vmcnt counts stay exact
             // (a conditional chunk makes it wait for every store of the previous chunks).
             using F0 = std::false_type;
             using F1 = std::true_type;
-            auto body = [&](int c, auto R_, auto MASK_, auto FIRST_) {
+            // C_h is recorded only in chunks that can be chunk hc of a split group (full waves: never in a ragged
+            // sweep): the one trip of the steady loop that holds it, and the tail.  hc >= 1, so never chunk 0.
+            using Cap = std::integral_constant<bool, SPLITOK && !RAG>;
+            auto body = [&](int c, auto R_, auto MASK_, auto FIRST_, auto CAP_) {
                 constexpr int r = decltype(R_)::value;
                 __builtin_amdgcn_sched_barrier(0);  // one chunk at a time: registers stay per chunk
                 CHUNKSTAMP(0, c);
 #pragma unroll
                 for (int k = 0; k < kChunk; ++k) E[(r + 1) & 1][k] = ld_em(Q[(r + 1) & 3], k);
-                Q[r] = loadpack(c + 4 < nch ? c + 4 : nch - 1);
-                chunk(c, E[r & 1], MASK_, FIRST_);
+                // the pack of chunk min(c + 4, nch - 1) (the add saturates: the last offsets reach up to 2^32)
+                const roff_t rnext = __builtin_elementwise_add_sat(roff, (roff_t)(4 * kRing));
+                Q[r] = at_byte(reinterpret_cast<const uint4 *>(symS), rnext < rmax ? rnext : rmax);
+                // This chunk's emissions were read a whole chunk ago.  One wait, for all but the kChunk reads just
+                // issued (LDS operations complete in order), replaces a wait in front of nearly every step.
+                // (The barrier keeps the scheduler from lifting the chain's first steps over the wait.)
+                if constexpr (LDSTAB) {
+                    __builtin_amdgcn_s_waitcnt(lgkmcnt_imm(kChunk));
+                    __builtin_amdgcn_sched_barrier(0);
+                }
+                chunk(c, E[r & 1], MASK_, FIRST_, CAP_);
             };
             auto tail_body = [&](int c, auto R_) {  // masked where the wave's last chunk is partial
-                if (RAG || (c == nch - 1 && (Tw % kChunk) != 0)) body(c, R_, F1{}, F0{});
-                else body(c, R_, F0{}, F0{});
+                if (RAG || (c == nch - 1 && (Tw % kChunk) != 0)) body(c, R_, F1{}, F0{}, Cap{});
+                else body(c, R_, F0{}, F0{}, Cap{});
             };
             using I0 = std::integral_constant<int, 0>;
             using I1 = std::integral_constant<int, 1>;
             using I2 = std::integral_constant<int, 2>;
             using I3 = std::integral_constant<int, 3>;
-            if (RAG || (nch == 1 && (Tw % kChunk) != 0)) body(0, I0{}, F1{}, F1{});
-            else body(0, I0{}, F0{}, F1{});
+            if (RAG || (nch == 1 && (Tw % kChunk) != 0)) body(0, I0{}, F1{}, F1{}, F0{});
+            else body(0, I0{}, F0{}, F1{}, F0{});
             const int lim = RAG ? nch : ((Tw % kChunk) != 0 ? nch - 1 : nch);  // chunks [1, lim) unmasked (full)
             int c = 1;
             using Mk = std::integral_constant<bool, RAG>;
             if constexpr (RAG) {  // ragged wave: chunks [1, Tmin / 8) have every lane active
                 for (; c + 4 <= Tmin / kChunk; c += 4) {
-                    body(c, I1{}, F0{}, F0{});
-                    body(c + 1, I2{}, F0{}, F0{});
-                    body(c + 2, I3{}, F0{}, F0{});
-                    body(c + 3, I0{}, F0{}, F0{});
+                    body(c, I1{}, F0{}, F0{}, F0{});
+                    body(c + 1, I2{}, F0{}, F0{}, F0{});
+                    body(c + 2, I3{}, F0{}, F0{}, F0{});
+                    body(c + 3, I0{}, F0{}, F0{}, F0{});
                 }
             }
-            auto trip = [&](int c0) {
-                body(c0, I1{}, Mk{}, F0{});
-                body(c0 + 1, I2{}, Mk{}, F0{});
-                body(c0 + 2, I3{}, Mk{}, F0{});
-                body(c0 + 3, I0{}, Mk{}, F0{});
+            auto trip = [&](int c0, auto CAP_) {
+                body(c0, I1{}, Mk{}, F0{}, CAP_);
+                body(c0 + 1, I2{}, Mk{}, F0{}, CAP_);
+                body(c0 + 2, I3{}, Mk{}, F0{}, CAP_);
+                body(c0 + 3, I0{}, Mk{}, F0{}, CAP_);
             };
-            for (; c + 4 <= lim; c += 4) trip(c);
+            if constexpr (Cap::value) {
+                // split groups: the steady loop up to the trip that holds chunk hc, that trip with the capture,
+                // and the loop again; every other wave runs the loop once (hc = -1: the first bound is lim)
+                const int lim0 = spl ? min(lim, hc) : lim;
+                for (; c + 4 <= lim0; c += 4) trip(c, F0{});
+                if (spl && c + 4 <= lim) {
+                    trip(c, F1{});
+                    c += 4;
+                    for (; c + 4 <= lim; c += 4) trip(c, F0{});
+                }
+            } else {
+                for (; c + 4 <= lim; c += 4) trip(c, F0{});
+            }
             if (c < nch) {
                 tail_body(c, I1{});
                 if (c + 1 < nch) {
@@ -805,7 +859,7 @@ __device__ __forceinline__ void estep_small_body(const EArgs &a, const long long
                 auto ldset = [&](int c) -> Ld {
                     Ld x;
                     x.ck = ZF ? 0.0 : ckw[(long long)c * kWave];
-                    x.sp = spw[(long long)c * U];
+                    x.sp = exps_at(c);
                     x.pk = loadpack(c);
                     return x;
                 };
@@ -864,7 +918,7 @@ __device__ __forceinline__ void estep_small_body(const EArgs &a, const long long
                 int s_hi = 0;                    // ... and that step's scale exponent
                 if (SPLIT && cl < (Tw - 1) / kChunk) {  // a lower range: step 8 cl + 8 is chunk cl + 1's first
                     const uint4 pn = loadpack(cl + 1);
-                    const int sn = exp_of(spw[(long long)(cl + 1) * U], 0);  // k = 0: always a scale step
+                    const int sn = exp_of(exps_at(cl + 1), 0);  // k = 0: always a scale step
                     if constexpr (PT) {
                         e_hi = ld_em(pn, 0);
                         s_hi = sn;
@@ -879,6 +933,10 @@ __device__ __forceinline__ void estep_small_body(const EArgs &a, const long long
                                  const unsigned (&hac)[kChunk], unsigned (&han)[kChunk], auto MASK_) {
                     constexpr bool MASK = decltype(MASK_)::value;
                     const uint4 &spA = cur.sp, &pkA = cur.pk;
+                    // (No explicit wait here, unlike the forward's: this chunk's rows were read at the end of the
+                    // previous chunk, just ahead of its histogram adds, not a chunk ahead.  One wait for all of them
+                    // before the chain measured slower than the compiler's wait per step, which lets the chain start
+                    // once the first two rows are there: cfg3 27.36 against 26.91 us)
                     int sk[kChunk];
                     double fs[kChunk], fus[kChunk];  // non-PT: b(o_t) / c_t for t = 8c .. 8c+7
 #pragma unroll

@@ -255,6 +255,30 @@ __device__ __forceinline__ char *lds_ptr(unsigned a) {
     return (char *)(lds_char *)(size_t)a;
 }
 
+// A pointer whose value is the same in every lane of the wave, said so to the compiler: it then lives in an
+// SGPR pair, and base + (32-bit per-lane byte offset) becomes the saddr form of global_load / global_store
+// (one VGPR of address, no 64-bit add).
+template <class T>
+__device__ __forceinline__ T *wave_uniform_ptr(T *p) {
+    const unsigned long long v = (unsigned long long)p;
+    const unsigned lo = __builtin_amdgcn_readfirstlane((unsigned)v);
+    const unsigned hi = __builtin_amdgcn_readfirstlane((unsigned)(v >> 32));
+    // (rebuilt as a pointer into global memory: from a bare integer the accesses would become flat ones)
+    typedef __attribute__((address_space(1))) T global_T;
+    return (T *)(global_T *)(((unsigned long long)hi << 32) | lo);
+}
+// The object of type T at base + off bytes (off unsigned, 32 or 64 bits wide: zero-extended, see wave_uniform_ptr)
+template <class T, class O>
+__device__ __forceinline__ T &at_byte(T *base, O off) {
+    static_assert(std::is_unsigned<O>::value, "byte offsets are unsigned");
+    using C = typename std::conditional<std::is_const<T>::value, const char, char>::type;
+    return *reinterpret_cast<T *>(reinterpret_cast<C *>(base) + (size_t)off);
+}
+
+// s_waitcnt immediate (gfx9 encoding) that waits until at most n LDS / scalar-memory operations are outstanding
+// and leaves vmcnt and expcnt alone
+constexpr int lgkmcnt_imm(int n) { return 0xC07F | (n << 8); }
+
 // ---------------------------------------------------------------------------------------------
 // Block reductions
 // ---------------------------------------------------------------------------------------------
