@@ -8,7 +8,8 @@ from .hmm_classes import DataStorageHMM, HMMTrained  # noqa: F401
 __all__ = ["HMMTrained", "DataStorageHMM", "hmm_training", "training_with_save", "get_observations",
            "calculate_log_likelihood", "viterbi_decode", "posterior_decode", "decode_words", "BaumWelchEngine",
            "lbg_train",
-           "createCodeVector", "save_centroids", "train_connected"]
+           "createCodeVector", "save_centroids", "train_connected", "frame_table", "mfcc_frames", "mfcc_recordings",
+           "encode_recordings"]
 
 
 def __getattr__(name):
@@ -24,6 +25,9 @@ def __getattr__(name):
     if name in ("lbg_train", "createCodeVector", "LBGResult"):
         from . import codevector as _cv
         return getattr(_cv, name)
+    if name in ("frame_table", "mfcc_frames", "mfcc_recordings", "encode_recordings"):
+        from . import frontend as _fe
+        return getattr(_fe, name)
     if name == "save_centroids":
         from .io import save_centroids
         return save_centroids

@@ -41,6 +41,7 @@ EXPORTED = (
     "hmmbw_cache_trim", "hmmbw_timing_split", "hmmbw_peer_region", "hmmbw_peer_ipc_handle", "hmmbw_peer_open",
     "hmmbw_peer_attach", "hmmbw_allreduce_kind", "hmmbw_status_live_wait", "hmmbw_get_option", "hmmbw_viterbi",
     "hmmbw_posterior", "hmmbw_lbg_train", "hmmbw_wordnet_decode", "hmmbw_embedded_train",
+    "hmmbw_mfcc", "hmmbw_mfcc_tables",
 )
 ABI_VERSION = 5
 OPT_SAFE_SCALING = 1
@@ -153,6 +154,12 @@ def _declare(lib):
                                            ctypes.c_int, ctypes.c_int, ctypes.c_double, ctypes.c_int64, ctypes.c_double,
                                            ctypes.c_double, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
                                            ctypes.c_void_p, ctypes.c_int64, P(ctypes.c_int64)]),
+        "hmmbw_mfcc_tables": (ctypes.c_int, [ctypes.c_int, ctypes.c_double, ctypes.c_int, ctypes.c_int, ctypes.c_void_p,
+                                             ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]),
+        "hmmbw_mfcc": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p, ctypes.c_int64,
+                                      ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int,
+                                      ctypes.c_void_p, ctypes.c_int, ctypes.c_double, ctypes.c_double, ctypes.c_void_p,
+                                      ctypes.c_int64]),
         "hmmbw_comm_probe": (ctypes.c_int, [ctypes.c_char_p]),
         "hmmbw_comm_unique_id": (ctypes.c_int, [ctypes.c_char_p, ctypes.c_void_p]),
         "hmmbw_comm_init": (ctypes.c_int, [c_ctx, ctypes.c_char_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_int,

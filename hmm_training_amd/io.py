@@ -5,9 +5,10 @@ frame JSON written by the reference's CodeVector pipeline.
 * ``*_frames.json``: ``[{"raw_samples": [...], "mfcc_vector": [...13], ...}, ...]``
   (codevector_classes.py:251-279, 477-495).
 
-Deviation (stated): the reference's RawDataMFCC.__post_init__ recomputes every frame's MFCC with
-librosa (codevector_classes.py:217-224); librosa is not part of this build, so the stored
-``mfcc_vector`` is used as-is.
+The reference's RawDataMFCC.__post_init__ recomputes every frame's MFCC with librosa each time a frame file is
+loaded (codevector_classes.py:217-224) and so ignores the stored ``mfcc_vector``.  ``load_frames`` uses the stored
+vector by default (stated deviation: no work, and files without raw samples load); ``recompute_mfcc=True`` does what
+the reference does, on the GPU (frontend.mfcc_frames).
 """
 from __future__ import annotations
 
@@ -46,8 +47,21 @@ def save_centroids(path: str, centroids) -> None:
         json.dump(data, fh, indent=2)
 
 
-def load_frames(path: str) -> List[Frame]:
+def load_frames(path: str, recompute_mfcc: bool = False) -> List[Frame]:
+    """The frames of a ``*_frames.json``.  ``recompute_mfcc``: every frame's MFCC is computed from its ``raw_samples``
+    at its ``sample_rate`` (RawDataMFCC.__post_init__, :217-224; a frame without samples keeps its stored vector)."""
     with open(path) as fh:
         data = json.load(fh)
-    return [Frame(mfcc=np.asarray(d["mfcc_vector"], dtype=np.float64).reshape(-1),
-                  frame_number=d.get("frame_number", 0), recording=d.get("recording", "")) for d in data]
+    frames = [Frame(mfcc=np.asarray(d["mfcc_vector"], dtype=np.float64).reshape(-1),
+                    frame_number=d.get("frame_number", 0), recording=d.get("recording", "")) for d in data]
+    if recompute_mfcc:
+        from .frontend import mfcc_frames
+        by_rate = {}
+        for i, d in enumerate(data):
+            if len(d.get("raw_samples", ())) > 0:
+                by_rate.setdefault(d.get("sample_rate", 16000), []).append(i)
+        for rate, idx in by_rate.items():
+            rows = mfcc_frames([np.asarray(data[i]["raw_samples"]) for i in idx], sample_rate=rate)
+            for i, row in zip(idx, rows):
+                frames[i].mfcc = row.copy()
+    return frames

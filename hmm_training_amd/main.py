@@ -1,10 +1,12 @@
-"""``train`` / ``test`` entry points of the reference's HMM/main.py (:46-197) on the MI355X engine, and
-``codebook``, the LBG training of the codebook they read (the reference's CodeVector pipeline).
+"""``train`` / ``test`` entry points of the reference's HMM/main.py (:46-197) on the MI355X engine,
+``codebook``, the LBG training of the codebook they read, and ``features``, the frame files both read (the
+reference's CodeVector pipeline).
 
     python -m hmm_training_amd.main train [--max-iterations 2] [--data ../Data]
     python -m hmm_training_amd.main test  [--data ../Data]
     python -m hmm_training_amd.main codebook --frames PATH [PATH ...] --out codevector.json
                                              [--centroids 256 --max-iterations 100 --epsilon 0.001]
+    python -m hmm_training_amd.main features --signals PATH.npy [PATH.npy ...] --out-dir DIR
 
 Same on-disk layout as the reference:
 * ``<data>/CodeVector/codevector.json`` — the codebook;
@@ -209,9 +211,36 @@ def codebook(frame_paths: List[str], out: str, centroids_quantity: int = 256, ma
     return centroids
 
 
+def features(signal_paths: List[str], out_dir: str, sample_rate: int = 16000) -> List[str]:
+    """Frame every processed signal (``Data/Processed/<word>/*.npy``) and compute its frames' MFCC on the GPU; write
+    ``<out_dir>/<stem>_frames.json`` with the fields of RawDataMFCC.to_dict (codevector_classes.py:252-264), which
+    ``codebook`` and ``load_all_recordings_by_word`` read.  Returns the paths written."""
+    import json
+
+    import numpy as np
+
+    from .frontend import frame_table, mfcc_recordings
+    signals = [np.asarray(np.load(p)).astype(float).flatten() for p in signal_paths]
+    rows = mfcc_recordings(signals, sample_rate=sample_rate)
+    os.makedirs(out_dir, exist_ok=True)
+    written = []
+    for path, sig, mf in zip(signal_paths, signals, rows):
+        stem = Path(path).stem
+        starts, lengths = frame_table(len(sig))
+        data = [{"raw_samples": sig[a:a + n].tolist(), "sample_rate": sample_rate, "n_channels": 1,
+                 "frame_duration_ms": 20.0, "mfcc_vector": mf[i].tolist(), "parent_centroid_id": 0, "generation": 0,
+                 "frame_number": i, "recording": stem} for i, (a, n) in enumerate(zip(starts, lengths))]
+        out = os.path.join(out_dir, f"{stem}_frames.json")
+        with open(out, "w") as fh:
+            json.dump(data, fh, indent=2)
+        print(f"    Saved {len(data)} frames to {out}")
+        written.append(out)
+    return written
+
+
 def _cli(argv=None):
     ap = argparse.ArgumentParser(description=__doc__.splitlines()[0])
-    ap.add_argument("command", choices=["train", "test", "codebook"])
+    ap.add_argument("command", choices=["train", "test", "codebook", "features"])
     ap.add_argument("--data", default="../Data")
     ap.add_argument("--models", default=None, help="model directory (default: DataStorageHMM's)")
     # `python main.py train` runs train_hmm(show_progress=True, max_iterations=2) (HMM/main.py:268);
@@ -223,7 +252,15 @@ def _cli(argv=None):
     ap.add_argument("--out", default=None, help="codebook: the codevector.json to write")
     ap.add_argument("--centroids", type=int, default=256)
     ap.add_argument("--epsilon", type=float, default=0.001)
+    ap.add_argument("--signals", nargs="+", default=None, help="features: processed signals (.npy)")
+    ap.add_argument("--out-dir", default=None, help="features: where the <stem>_frames.json files go")
+    ap.add_argument("--sample-rate", type=int, default=16000)
     a = ap.parse_args(argv)
+    if a.command == "features":
+        if not a.signals or not a.out_dir:
+            ap.error("features needs --signals and --out-dir")
+        features(a.signals, a.out_dir, sample_rate=a.sample_rate)
+        return 0
     if a.command == "codebook":
         if not a.frames or not a.out:
             ap.error("codebook needs --frames and --out")

@@ -43,7 +43,9 @@ extern "C" {
                                  lacks the symbol; hmmbw_lbg_train is a new entry point of version 5: an older
                                  library lacks the symbol; hmmbw_wordnet_decode is a new entry point of version
                                  5: an older library lacks the symbol; hmmbw_embedded_train is a new entry point
-                                 of version 5: an older library lacks the symbol) */
+                                 of version 5: an older library lacks the symbol; hmmbw_mfcc and
+                                 hmmbw_mfcc_tables are new entry points of version 5: an older library lacks the
+                                 symbols) */
 
 #define HMMBW_OK 0
 #define HMMBW_E_INVALID (-1)        /* bad argument (shape, range, null pointer)             */
@@ -504,6 +506,37 @@ int hmmbw_lbg_train(void *stream, const double *frames, int64_t n_frames, int fr
                     int n_centroids, double epsilon, int64_t max_iterations, double split_up, double split_down,
                     double *centroids, double *generations, int32_t *assignments,
                     hmmbw_lbg_record *records, int64_t records_cap, int64_t *n_records);
+
+/* ---- MFCC front end: the rows hmmbw_vq_encode and hmmbw_lbg_train read ----
+ * RawDataMFCC.calculate_mfcc, CodeVector/codevector_classes.py:226-250: librosa.feature.mfcc(y = frame, sr, n_mfcc,
+ * n_fft = len(frame), hop_length = None, center = False, n_mels), one call per frame there.  For a frame x of L =
+ * frame_len samples (one STFT column, no padding):
+ *   y[n] = x[n] window[n];  P[k] = |sum_n y[n] exp(-2 pi i k n / L)|^2, k = 0 .. L/2;  M[m] = sum_k mel[m][k] P[k];
+ *   dB[m] = 10 log10(max(amin, M[m])), then dB[m] = max(dB[m], max_m dB - top_db) unless top_db < 0 (floor off);
+ *   out[f * out_stride + i] = sum_m dct[i][m] dB[m], i = 0 .. n_mfcc - 1.
+ * A frame with a NaN or +-Inf sample gets n_mfcc zeros (librosa rejects such audio and calculate_mfcc keeps its
+ * zeros, :247-250); its neighbours are not affected.  A silent frame gives dB = 10 log10(amin) throughout.
+ * The tables are arguments, not constants of the kernel.  hmmbw_mfcc_tables fills HOST arrays with librosa's
+ * defaults: window [frame_len], the periodic Hann window; twiddle [frame_len][2], cos and sin of 2 pi m / frame_len;
+ * mel [n_mels][frame_len / 2 + 1], the Slaney-scale, Slaney-normalised filter bank from 0 to sample_rate / 2, each
+ * weight a float32 value as librosa stores it; dct [n_mfcc][n_mels], the first rows of the orthonormal DCT-II.
+ * HMMBW_E_INVALID: frame_len < 2, sample_rate <= 0 or NaN, n_mels < 1, n_mfcc < 1 or > n_mels, a null pointer;
+ * HMMBW_E_UNSUPPORTED: frame_len > 512 or n_mels > 64. */
+int hmmbw_mfcc_tables(int frame_len, double sample_rate, int n_mels, int n_mfcc, double *window, double *twiddle,
+                      double *mel, double *dct);
+/* DEVICE pointers throughout: samples fp64 [n_samples]; frame_starts int64 [n_frames], offsets into samples (frames
+ * may overlap: they are views, never copies); the four tables as hmmbw_mfcc_tables lays them out; out fp64, row f at
+ * out + f * out_stride with out_stride >= n_mfcc (13 writes straight into a stride-13 frame buffer; the columns past
+ * n_mfcc are not touched).  One call serves one frame length.  Enqueued on `stream` (hipStream_t, NULL = legacy
+ * default); the device is the current one.  The frame table is on the device, so the call first runs a range check
+ * over it on `stream` and waits for its 4-byte answer; the MFCC kernel itself is then enqueued and the call returns
+ * without waiting for it, as hmmbw_vq_encode does.
+ * HMMBW_E_INVALID: a null pointer, n_frames < 0, frame_len < 2, a frame that starts before 0 or runs past n_samples,
+ * n_mels < 1, n_mfcc < 1 or > n_mels, out_stride < n_mfcc, amin <= 0 or NaN.  HMMBW_E_UNSUPPORTED: frame_len > 512
+ * or n_mels > 64 (the 16-frame tile's LDS).  n_frames == 0 returns HMMBW_OK and launches nothing. */
+int hmmbw_mfcc(void *stream, const double *samples, int64_t n_samples, const int64_t *frame_starts, int64_t n_frames,
+               int frame_len, const double *window, const double *twiddle, const double *mel, int n_mels,
+               const double *dct, int n_mfcc, double amin, double top_db, double *out, int64_t out_stride);
 
 /* ---- Groups: several models of one shape, one launch per EM iteration / per scoring pass ----
  * The reference trains its word models one after another (train_hmm, HMM/main.py:147-152, calling
