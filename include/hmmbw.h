@@ -547,8 +547,13 @@ int hmmbw_mfcc(void *stream, const double *samples, int64_t n_samples, const int
  * stop rule, exactly as if trained alone) and scores all of them with one launch.
  * Members: single-rank contexts on the same device and stream, with equal N, M and resolved topology,
  * N <= 16 and emission tables that fit LDS, each with observations and parameters set (checked at
- * creation, HMMBW_E_UNSUPPORTED otherwise, and again at every call); the group does not own them
- * (destroy the group first). */
+ * creation, HMMBW_E_UNSUPPORTED otherwise, and again at every call, where a member that no longer fits
+ * is refused before any member is touched); the group does not own them (destroy the group first).
+ * A member may hold no sequences (hmmbw_set_observations with R = 0): it is accepted, owns no workgroup
+ * of the grouped launches and does exactly what hmmbw_iterate and hmmbw_score do for it alone: every
+ * iteration records L = -inf and diff = +inf and re-estimates all-zero parameters until max_iterations,
+ * and it adds nothing to hmmbw_group_score's output.  Its M-step cannot run in a slice's prologue, so a
+ * group with such a member iterates one launch at a time (tests/test_gpu_group_shapes.py). */
 typedef struct hmmbw_group hmmbw_group;
 int hmmbw_group_create(hmmbw_ctx *const *ctxs, int n, hmmbw_group **out);
 int hmmbw_group_destroy(hmmbw_group *group);

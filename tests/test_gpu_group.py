@@ -2,7 +2,13 @@
 E-step launch per EM iteration and scored by one launch, each member against the oracle run alone
 (the reference trains word by word, HMM/main.py:147-152, and scores pair by pair,
 HMM/hmm_testing.py:139-161).  Same tolerances as test_gpu_parity.py; iteration counts, stop flags
-and printed lines exact."""
+and printed lines exact.
+
+Every group here has members of one size (word_set: R sequences each, one or two workgroups per member).  What
+real use adds is in test_gpu_group_shapes.py: slices of unequal length in every order, a member on the spread map
+and one of more than 512 workgroups, options that differ between members, enqueues that span and wrap the argument
+slabs, a score while an M-step is pending, members that change or hold no sequences under the group, and spies
+that show hmm_training_group and score_matrix really group."""
 import contextlib
 import io
 
