@@ -6,7 +6,8 @@ the EM hot path runs in hand-written gfx950 HIP kernels behind the C ABI of incl
 from .hmm_classes import DataStorageHMM, HMMTrained  # noqa: F401
 
 __all__ = ["HMMTrained", "DataStorageHMM", "hmm_training", "training_with_save", "get_observations",
-           "calculate_log_likelihood", "viterbi_decode", "posterior_decode", "decode_words", "BaumWelchEngine",
+           "calculate_log_likelihood", "viterbi_decode", "posterior_decode", "decode_words", "align_words",
+           "BaumWelchEngine",
            "lbg_train",
            "createCodeVector", "save_centroids", "train_connected", "frame_table", "mfcc_frames", "mfcc_recordings",
            "encode_recordings"]
@@ -19,7 +20,7 @@ def __getattr__(name):
         from . import hmm_training as _ht
         return getattr(_ht, name)
     if name in ("calculate_log_likelihood", "score_matrix", "test_hmm", "viterbi_decode", "posterior_decode",
-                "decode_words", "segments_from_path"):
+                "decode_words", "align_words", "segments_from_path"):
         from . import hmm_testing as _te
         return getattr(_te, name)
     if name in ("lbg_train", "createCodeVector", "LBGResult"):

@@ -6,7 +6,7 @@ alloc.hip: block cache and allocation ledger; peer.hip: peer all-reduce; comm.hi
 group.hip: grouped launches; viterbi.hip: the Viterbi decoder and its kernels; posterior.hip: the state
 posteriors and their kernels; lbg.hip: LBG codebook training and its kernels; wordnet.hip: connected-word
 decoding and its kernels; embedded.hip: embedded training over transcribed word sequences and its kernels;
-mfcc.hip: the MFCC front end and its kernel), the VQ
+mfcc.hip: the MFCC front end and its kernel; align.hip: forced alignment to a transcript and its kernels), the VQ
 encoder (csrc/vq.hip), one small-N E-step instantiation unit per
 state count N = 1..16 (csrc/estep_small_inst.hip with -DHMMBW_INST_N=n) and the wide-N unit
 (csrc/estep_wide_inst.hip).
@@ -41,7 +41,7 @@ def units():
     u = [(SRC, [], "hmmbw"), (os.path.join(CSRC, "estep_wide_inst.hip"), wide_flags, "estep_wide"),
          (os.path.join(CSRC, "vq.hip"), [], "vq")]
     u += [(os.path.join(CSRC, s + ".hip"), [], s) for s in ("alloc", "peer", "comm", "group", "viterbi", "posterior",
-                                                            "lbg", "wordnet", "embedded", "mfcc")]
+                                                            "lbg", "wordnet", "embedded", "mfcc", "align")]
     u += [(os.path.join(CSRC, "estep_small_inst.hip"), [f"-DHMMBW_INST_N={n}"], f"estep_small_n{n}")
           for n in SMALL_N]
     return u

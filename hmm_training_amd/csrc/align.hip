@@ -1,0 +1,477 @@
+// align.hip — forced alignment (hmmbw_align, include/hmmbw.h) for gfx950: the Viterbi path of every loaded
+// utterance through the chain of word models its transcript names (a bank: pi [W][N], A [W][N][N], B [W][N][K]; a
+// transcript w_0 .. w_{L-1} of word ids), its log-probability and the frame at which every instance starts.  The
+// hard-decision counterpart of embedded.hip's E-step on the same chain, with wordnet.hip's log-domain step,
+// back-pointers and in-kernel backtrace.
+//
+// Log domain, fp64, no rescaling; composite state (l, j), l the transcript position, has index l N + j:
+//   delta_0(0,j)  = log pi_{w_0}[j] + log b_{w_0,j}(o_0);   delta_0(l>0, .) = -inf
+//   inner_t(l,j)  = max_i delta_{t-1}(l,i) + log a_{w_l}[i][j]       the smallest i on ties
+//   entry_t(l,j)  = delta_{t-1}(l-1,N-1) + log pi_{w_l}[j]           -inf for l = 0
+//   delta_t(l,j)  = (entry_t > inner_t ? entry_t : inner_t) + log b_{w_l,j}(o_t)     the within-word arc wins ties
+// log 0 = -inf; no +inf ever occurs, so -inf + x never makes a NaN and a -inf candidate never beats a finite one.
+//
+// k_align_prep builds the log tables (align_plan.hpp: EmbedTab's layout) from the staged linear bank once per call,
+// with the log of k_wordnet_prep.  k_align gives every utterance a group of GW lanes (8, 16, 32 or 64), lane l =
+// transcript position l, and reads the symbols from the context's own packs as the two siblings do; a wave holds
+// the 64 / GW consecutive layout slots.  The lane keeps its instance's N deltas, its word's log pi and log A (2
+// values per state for left-to-right banks, N^2 for dense ones) in registers.  The only cross-lane work of a step is
+// the left neighbour's delta(l-1, N-1), a one-lane shift: the entry source is fixed by the chain, so there is no
+// max over words as in k_wordnet.  The emissions of the next step are loaded while the current step computes.
+// With paths, a step's back-pointers go to HBM as 4 bytes per lane (a nibble per state: the within-word
+// predecessor and the entry-arc bit), one coalesced 256-byte row per step and wave; the backtrace runs in the same
+// kernel and loads eight steps' rows at a time, so the dependent step is a cross-lane pick from lane l, never a
+// memory access.  Lanes past the transcript's end and padding slots hold -inf throughout and write nothing.
+#include "host.hpp"
+#include "align_plan.hpp"
+#include "lane_ops.hpp"
+
+namespace hmmbw {
+
+struct AlArgs {
+    const uint16_t *sym;
+    const long long *wave_symoff;
+    const int *slot_len, *slot_seq;
+    const long long *slot_out, *psi_off;
+    const long long *word_off;   // [R + 1] transcripts, CSR in caller order
+    const int *word_ids;
+    const double *tab;           // align_tab
+    unsigned *bp;                // [row][64 lanes]
+    double *logp;
+    int32_t *path;
+    int32_t *bounds;
+    long long nslots;
+    long long o_A, o_B;          // table offsets (pi is at 0)
+    int U, W, K;
+    int shift;                   // pack entry -> symbol: >> shift, or / div when shift < 0
+    int div;
+    int lds;                     // the emission table is copied to LDS
+    int end_final;               // only (L - 1, N - 1) competes for the end
+};
+
+// in: pi [W][N] | A [W][N][N] | B [W][N][K]
+__global__ void __launch_bounds__(256) k_align_prep(const double *__restrict__ in, int W, int N, int K, EmbedTab o,
+                                                    double *__restrict__ tab) {
+    const int NP = embed_np(N);
+    const double *pi = in, *A = pi + (long long)W * N, *B = A + (long long)W * N * N;
+    for (long long e = (long long)blockIdx.x * blockDim.x + threadIdx.x; e < o.total; e += (long long)gridDim.x * blockDim.x) {
+        double v = 0.0;  // log 0 = -inf below
+        if (e < o.A) {
+            const int w = (int)(e / NP), j = (int)(e % NP);
+            if (j < N) v = pi[w * N + j];
+        } else if (e < o.B) {
+            if (e - o.A < (long long)W * N * N) v = A[e - o.A];
+        } else {
+            const long long x = e - o.B;
+            const long long k = x / ((long long)W * NP);
+            const int w = (int)(x / NP % W), j = (int)(x % NP);
+            if (j < N) v = B[((long long)w * N + j) * K + k];
+        }
+        tab[e] = log(v);
+    }
+}
+
+// the value of lane l - 1 of the group, -inf at the group's left edge
+template <int GW>
+__device__ __forceinline__ double al_from_left(double x, int l) {
+    double nb;
+    if constexpr (GW <= 16) nb = dpp<0x111>(x);  // row_shr:1
+    else nb = __shfl_up(x, 1, GW);
+    return l > 0 ? nb : -INFINITY;
+}
+
+// a lane's N values of one table row (NP doubles, 16-B aligned when NP >= 2)
+template <int N>
+__device__ __forceinline__ void al_load_row(const double *p, double (&r)[N]) {
+    if constexpr (N == 1) {
+        r[0] = p[0];
+    } else {
+        const double2 *p2 = reinterpret_cast<const double2 *>(p);
+#pragma unroll
+        for (int h = 0; h < (N + 1) / 2; ++h) {
+            const double2 x = p2[h];
+            r[2 * h] = x.x;
+            if (2 * h + 1 < N) r[2 * h + 1] = x.y;
+        }
+    }
+}
+
+template <int GW, int N, bool LR, bool PATH>
+__global__ void __launch_bounds__(kVitBlock) k_align(AlArgs a) {
+    extern __shared__ __attribute__((aligned(16))) double sB[];  // a.lds: log B [K][W][NP]
+    constexpr int NP = embed_np(N);
+    constexpr int SPW = kVitWave / GW;
+    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+    const int l = lane & (GW - 1);
+    const double *tabB = a.tab + a.o_B;
+    if (a.lds) {
+        for (int i = threadIdx.x; i < a.K * a.W * NP; i += kVitBlock) sB[i] = tabB[i];
+        __syncthreads();
+    }
+
+    const long long vw = (long long)blockIdx.x * (kVitBlock / kVitWave) + wv;
+    const long long s = vw * SPW + lane / GW;
+    const bool real = s < a.nslots;
+    const int T = real ? a.slot_len[s] : 0;     // 0 in padding slots
+    const int seq = real ? a.slot_seq[s] : -1;  // -1 in padding slots
+    int Tw = T;  // the wave's longest utterance
+#pragma unroll
+    for (int m = GW; m < kVitWave; m <<= 1) Tw = max(Tw, __shfl_xor(Tw, m));
+    if (Tw == 0) return;
+
+    // the lane's instance: position l of the utterance's transcript (lanes past its end hold -inf throughout)
+    int Lw = 0;
+    long long woff = 0;
+    if (seq >= 0) {
+        woff = a.word_off[seq];
+        Lw = (int)(a.word_off[seq + 1] - woff);
+    }
+    const bool live = l < Lw;
+    const int wid = live ? a.word_ids[woff + l] : 0;
+    const size_t kstride = (size_t)a.W * NP, wrow = (size_t)wid * NP;
+    const double *lbt = (a.lds ? sB : tabB) + wrow;
+
+    // chunk c of the slot: 8 steps in one 16-B load, U loads further on per chunk (pack_pos)
+    const uint4 *pk = reinterpret_cast<const uint4 *>(a.sym) +
+                      (real ? pack_pos(a.wave_symoff[s / a.U], a.U, (int)(s % a.U), 0) / kChunk : 0);
+    auto chunk = [&](int t0) {
+        uint4 q = make_uint4(0, 0, 0, 0);
+        if (t0 < T) q = pk[(long long)(t0 / kChunk) * a.U];
+        return q;
+    };
+    auto row_of = [&](unsigned e) {  // symbol 0's row past the slot's end (unused)
+        const unsigned o = a.shift >= 0 ? e >> a.shift : e / (unsigned)a.div;
+        return lbt + (size_t)o * kstride;
+    };
+
+    double la[LR ? 2 * N : N * N];  // LR: log a_{j-1,j}, log a_jj per state j | dense: log a_ij row-major
+    {
+        const double *tA = a.tab + a.o_A + (long long)wid * N * N;
+        if constexpr (LR) {
+#pragma unroll
+            for (int j = 0; j < N; ++j) {
+                la[2 * j] = live && j > 0 ? tA[(j - 1) * N + j] : -INFINITY;
+                la[2 * j + 1] = live ? tA[j * N + j] : -INFINITY;
+            }
+        } else {
+#pragma unroll
+            for (int i = 0; i < N * N; ++i) la[i] = live ? tA[i] : -INFINITY;
+        }
+    }
+    double lpi[N];
+    al_load_row<N>(a.tab + wrow, lpi);
+#pragma unroll
+    for (int j = 0; j < N; ++j) lpi[j] = live ? lpi[j] : -INFINITY;
+    unsigned *bp = nullptr;
+    if constexpr (PATH) bp = a.bp + a.psi_off[vw] * kVitWave + lane;  // row t: bp[t * 64]
+
+    double d[N];  // delta_{T-1}(l, .) once the slot's steps are done
+#pragma unroll
+    for (int j = 0; j < N; ++j) d[j] = -INFINITY;
+
+    uint4 qn = chunk(0);
+    double lbn[N];  // the next step's emissions
+    al_load_row<N>(row_of(qn.x & 0xffffu), lbn);
+    for (int t0 = 0; t0 < Tw; t0 += kChunk) {
+        const uint4 q = qn;
+        qn = chunk(t0 + kChunk);
+        const unsigned long long qlo = q.x | (unsigned long long)q.y << 32, qhi = q.z | (unsigned long long)q.w << 32;
+#pragma nounroll
+        for (int k = 0; k < kChunk; ++k) {
+            const int t = t0 + k;
+            double lb[N];
+#pragma unroll
+            for (int j = 0; j < N; ++j) lb[j] = lbn[j];
+            {
+                const int kn = k + 1;
+                const unsigned long long word = kn < 4 ? qlo : kn < 8 ? qhi : (unsigned long long)qn.x;
+                al_load_row<N>(row_of((unsigned)(word >> (16 * (kn & 3))) & 0xffffu), lbn);
+            }
+            double nd[N];
+            unsigned nib = 0;
+            if (t == 0) {
+#pragma unroll
+                for (int j = 0; j < N; ++j) nd[j] = l == 0 ? lpi[j] + lb[j] : -INFINITY;
+            } else {
+                const double left = al_from_left<GW>(d[N - 1], l);
+#pragma unroll
+                for (int j = 0; j < N; ++j) {
+                    double best;
+                    int arg;
+                    if constexpr (LR) {
+                        best = d[j > 0 ? j - 1 : 0] + la[2 * j];  // la[0] = -inf
+                        arg = j > 0 ? j - 1 : 0;
+                        const double self = d[j] + la[2 * j + 1];
+                        arg = self > best ? j : arg;
+                        best = self > best ? self : best;
+                    } else {
+                        best = d[0] + la[j];
+                        arg = 0;
+#pragma unroll
+                        for (int i = 1; i < N; ++i) {
+                            const double c = d[i] + la[i * N + j];
+                            arg = c > best ? i : arg;
+                            best = c > best ? c : best;
+                        }
+                    }
+                    const double entry = left + lpi[j];
+                    const bool in = entry > best;
+                    nd[j] = (in ? entry : best) + lb[j];
+                    nib |= (unsigned)(arg | (in ? 8 : 0)) << (4 * j);
+                }
+            }
+            if (t < T) {
+#pragma unroll
+                for (int j = 0; j < N; ++j) d[j] = nd[j];
+                if constexpr (PATH) bp[(long long)t * kVitWave] = nib;
+            }
+        }
+    }
+
+    // the end state: the smallest j attaining the largest delta_{T-1}(L-1, j), found on lane L - 1 and broadcast
+    double v = d[N - 1];
+    int cj = N - 1;
+    if (!a.end_final) {
+        v = d[0];
+        cj = 0;
+#pragma unroll
+        for (int j = 1; j < N; ++j) {
+            cj = d[j] > v ? j : cj;
+            v = d[j] > v ? d[j] : v;
+        }
+    }
+    const int tail = max(Lw - 1, 0);
+    v = __shfl(v, tail, GW);
+    cj = __shfl(cj, tail, GW);
+    if (seq >= 0 && l == 0) a.logp[seq] = v;
+
+    if constexpr (PATH) {
+        const bool valid = v > -INFINITY;
+        const long long out = seq >= 0 ? a.slot_out[s] : 0;
+        if (live && !valid) a.bounds[woff + l] = -1;
+        int cl = tail;
+        for (int t0 = (Tw - 1) / kChunk * kChunk; t0 >= 0; t0 -= kChunk) {
+            unsigned p[kChunk];
+#pragma unroll
+            for (int k = 0; k < kChunk; ++k) p[k] = t0 + k < T ? bp[(long long)(t0 + k) * kVitWave] : 0u;
+            int ws = -1, wb = -1;  // lane k of the group writes step t0 + k
+#pragma unroll
+            for (int k = kChunk - 1; k >= 0; --k) {
+                const unsigned pw = (unsigned)__shfl((int)p[k], cl, GW);  // the back-pointers of position cl
+                if (t0 + k < T) {
+                    const unsigned nb = (pw >> (4 * cj)) & 15u;
+                    const bool in = (nb & 8u) != 0;  // never set at t = 0, nor on lane 0
+                    if (l == k) {
+                        ws = cl * N + cj;
+                        wb = (in || t0 + k == 0) ? cl : -1;
+                    }
+                    cj = in ? N - 1 : (int)(nb & 7u);
+                    cl = in ? cl - 1 : cl;
+                }
+            }
+            if (seq >= 0 && l < kChunk && t0 + l < T) {
+                a.path[out + t0 + l] = valid ? ws : -1;
+                if (valid && wb >= 0) a.bounds[woff + wb] = t0 + l;
+            }
+        }
+    }
+}
+
+using AlFn = void (*)(AlArgs);
+
+template <int GW, int N>
+static AlFn al_kernel3(bool lr, bool path) {
+    if (lr) return path ? k_align<GW, N, true, true> : k_align<GW, N, true, false>;
+    return path ? k_align<GW, N, false, true> : k_align<GW, N, false, false>;
+}
+
+template <int GW>
+static AlFn al_kernel2(int N, bool lr, bool path) {
+    switch (N) {
+        case 1: return al_kernel3<GW, 1>(lr, path);
+        case 2: return al_kernel3<GW, 2>(lr, path);
+        case 3: return al_kernel3<GW, 3>(lr, path);
+        case 4: return al_kernel3<GW, 4>(lr, path);
+        case 5: return al_kernel3<GW, 5>(lr, path);
+        case 6: return al_kernel3<GW, 6>(lr, path);
+        case 7: return al_kernel3<GW, 7>(lr, path);
+        default: return al_kernel3<GW, 8>(lr, path);
+    }
+}
+
+static AlFn al_kernel(int GW, int N, bool lr, bool path) {
+    switch (GW) {
+        case 8: return al_kernel2<8>(N, lr, path);
+        case 16: return al_kernel2<16>(N, lr, path);
+        case 32: return al_kernel2<32>(N, lr, path);
+        default: return al_kernel2<64>(N, lr, path);
+    }
+}
+
+void align_free(hmmbw_ctx *c) {
+    hmmbw_ctx::Align &n = c->al;
+    dfree(n.d_psi_off); dfree(n.d_in); dfree(n.d_tab); dfree(n.d_word_off); dfree(n.d_word_ids); dfree(n.d_path);
+    dfree(n.d_bounds); dfree(n.d_bp);
+    n = hmmbw_ctx::Align{};
+}
+
+// a buffer of at least n elements: kept while it is large enough
+template <class T>
+static int al_grow(hmmbw_ctx *c, T *&p, size_t &have, size_t n) {
+    if (p && have >= n) return HMMBW_OK;
+    sync_ctx(c);
+    dfree(p);
+    have = 0;
+    if (int rc = dalloc(&p, n)) return rc;
+    have = n;
+    return HMMBW_OK;
+}
+
+// the aligner's buffers for the loaded observations, this bank shape and these transcripts: the back-pointer row
+// offsets of the group width, the staging and table buffers, the transcripts, and with paths the path, the bounds
+// and the back-pointers
+static int align_buffers(hmmbw_ctx *c, int GW, size_t n_in, size_t n_tab, size_t n_pos, bool path) {
+    if (int rc = viterbi_plan_ready(c)) return rc;  // slot_out and the device logp
+    hmmbw_ctx::Align &n = c->al;
+    if (n.GW != GW) {
+        sync_ctx(c);
+        dfree(n.d_psi_off);
+        dfree(n.d_bp);
+        n.GW = 0;
+        ViterbiPlan P = plan_viterbi_group(c->h_slen, c->h_sseq, c->R, GW);
+        if (int rc = dalloc(&n.d_psi_off, P.psi_off.size())) return rc;
+        if (!P.psi_off.empty())
+            HIP_TRY(hipMemcpy(n.d_psi_off, P.psi_off.data(), sizeof(long long) * P.psi_off.size(), hipMemcpyHostToDevice));
+        n.rows = P.psi_rows;
+        n.nvw = P.nvw;
+        n.GW = GW;
+    }
+    if (int rc = al_grow(c, n.d_in, n.n_in, n_in)) return rc;
+    if (int rc = al_grow(c, n.d_tab, n.n_tab, n_tab)) return rc;
+    if (int rc = al_grow(c, n.d_word_ids, n.n_ids, n_pos)) return rc;
+    if (!n.d_word_off)
+        if (int rc = dalloc(&n.d_word_off, (size_t)c->R + 1)) return rc;
+    if (path) {
+        int rc = al_grow(c, n.d_bounds, n.n_bounds, n_pos);
+        if (!rc && !n.d_path) rc = dalloc(&n.d_path, (size_t)c->vit.plan.total);
+        if (rc) return rc;
+        if (!n.d_bp)
+            if (int rc2 = dalloc(&n.d_bp, (size_t)n.rows * kVitWave))
+                return fail(rc2, "the alignment back-pointers (" + std::to_string(align_bp_bytes(n.rows)) +
+                                     " bytes) do not fit: " + g_err);
+    }
+    return HMMBW_OK;
+}
+
+}  // namespace hmmbw
+
+extern "C" int hmmbw_align(hmmbw_ctx *c, int n_words, const double *pi, const double *A, const double *B,
+                           const int64_t *word_offsets, const int32_t *word_ids, int64_t n_seq, int flags,
+                           double *logp_out, int32_t *path_out, int64_t path_len, int32_t *bounds_out,
+                           int64_t bounds_len) {
+    if (!c) return fail(HMMBW_E_INVALID, "null context");
+    if (!c->has_obs) return fail(HMMBW_E_STATE, "observations not set");
+    if (int rc = set_device(c)) return rc;
+    if (n_words < 1) return fail(HMMBW_E_INVALID, "n_words " + std::to_string(n_words) + " < 1");
+    if (!pi || !A || !B || !word_offsets || !word_ids || !logp_out) return fail(HMMBW_E_INVALID, "null argument");
+    if (bounds_out && !path_out) return fail(HMMBW_E_INVALID, "bounds_out needs path_out");
+    if (!align_flags_ok(flags)) return fail(HMMBW_E_INVALID, "unknown flag");
+    if (n_seq != c->R)
+        return fail(HMMBW_E_INVALID, "n_seq " + std::to_string(n_seq) + " is not the number of loaded sequences (" +
+                                         std::to_string(c->R) + ")");
+    if (n_words > kAlMaxWords)
+        return fail(HMMBW_E_UNSUPPORTED, "n_words " + std::to_string(n_words) + " > " + std::to_string(kAlMaxWords));
+    if (c->N > kAlMaxStates)
+        return fail(HMMBW_E_UNSUPPORTED, "word models of N " + std::to_string(c->N) + " > " + std::to_string(kAlMaxStates) + " states");
+    const int W = n_words, N = c->N, K = c->K;
+    if (!wordnet_weights_ok(pi, (long long)W * N) || !wordnet_weights_ok(A, (long long)W * N * N) ||
+        !wordnet_weights_ok(B, (long long)W * N * K))
+        return fail(HMMBW_E_INVALID, "a negative, infinite or NaN bank parameter");
+    long long longest = 0;
+    switch (embed_transcripts_check(word_offsets, word_ids, n_seq, W, &longest, nullptr)) {
+        case 0: break;
+        case 1: return fail(HMMBW_E_INVALID, "an empty transcript");
+        case 2: return fail(HMMBW_E_INVALID, "a word id outside [0, " + std::to_string(W) + ")");
+        default: return fail(HMMBW_E_INVALID, "word_offsets do not start at 0 or decrease");
+    }
+    if (longest > kAlMaxWords)
+        return fail(HMMBW_E_UNSUPPORTED, "a transcript of " + std::to_string(longest) + " words > " + std::to_string(kAlMaxWords));
+    if (int rc = check_closed(c)) return rc;
+    long long total = 0;
+    for (int T : c->h_slen) total += T;
+    const long long n_pos = n_seq > 0 ? word_offsets[n_seq] : 0;
+    switch (align_lengths_check(path_len, total, bounds_len, n_pos)) {
+        case 0: break;
+        case 1:
+            return fail(HMMBW_E_INVALID, "path_len " + std::to_string(path_len) + " is not the number of loaded symbols (" +
+                                             std::to_string(total) + ")");
+        default:
+            return fail(HMMBW_E_INVALID, "bounds_len " + std::to_string(bounds_len) +
+                                             " is not the number of transcript positions (" + std::to_string(n_pos) + ")");
+    }
+    if (c->R == 0) return HMMBW_OK;
+
+    const bool path = path_out != nullptr;
+    const bool lr = !(flags & HMMBW_ALIGN_DENSE) && wordnet_is_lr(A, W, N);
+    const int GW = align_gw((int)longest);
+    const EmbedTab o = align_tab(W, N, K);
+    const long long n_in = embed_bank_len(W, N, K);
+    if (int rc = align_buffers(c, GW, (size_t)n_in, (size_t)o.total, (size_t)n_pos, path)) return rc;
+    hmmbw_ctx::Align &n = c->al;
+
+    // the bank, staged as one block: pi | A | B; the transcripts as the kernel's types
+    std::vector<double> h((size_t)n_in);
+    {
+        double *hp = std::copy(pi, pi + (long long)W * N, h.data());
+        hp = std::copy(A, A + (long long)W * N * N, hp);
+        std::copy(B, B + (long long)W * N * K, hp);
+    }
+    HIP_TRY(hipMemcpy(n.d_in, h.data(), sizeof(double) * (size_t)n_in, hipMemcpyHostToDevice));
+    {
+        std::vector<long long> off(word_offsets, word_offsets + n_seq + 1);
+        std::vector<int> ids(word_ids, word_ids + n_pos);
+        HIP_TRY(hipMemcpy(n.d_word_off, off.data(), sizeof(long long) * off.size(), hipMemcpyHostToDevice));
+        HIP_TRY(hipMemcpy(n.d_word_ids, ids.data(), sizeof(int) * ids.size(), hipMemcpyHostToDevice));
+    }
+    hipLaunchKernelGGL(k_align_prep, dim3((unsigned)std::min<long long>((o.total + 255) / 256, 1024)), dim3(256), 0,
+                       c->stream, (const double *)n.d_in, W, N, K, o, n.d_tab);
+    HIP_TRY(hipGetLastError());
+
+    AlArgs a{};
+    a.sym = c->d_sym;  // never d_sym2: the row tables' packs (or symbol ids)
+    a.wave_symoff = c->d_wsym;
+    a.slot_len = c->d_slen;
+    a.slot_seq = c->d_sseq;
+    a.slot_out = c->vit.d_slot_out;
+    a.psi_off = n.d_psi_off;
+    a.word_off = n.d_word_off;
+    a.word_ids = n.d_word_ids;
+    a.tab = n.d_tab;
+    a.bp = path ? n.d_bp : nullptr;
+    a.logp = c->vit.d_logp;
+    a.path = path ? n.d_path : nullptr;
+    a.bounds = path ? n.d_bounds : nullptr;
+    a.nslots = c->vit.plan.nslots;
+    a.o_A = o.A;
+    a.o_B = o.B;
+    a.U = c->U;
+    a.W = W;
+    a.K = K;
+    const long long div = viterbi_pack_div(c->lds_tables(), c->G, 0);  // rows of G entries, no pad column
+    a.div = (int)div;
+    a.shift = viterbi_pack_shift(div);
+    a.lds = embed_emis_in_lds(K, W, N) ? 1 : 0;
+    a.end_final = (flags & HMMBW_ALIGN_END_FINAL) ? 1 : 0;
+    const AlFn fn = al_kernel(GW, N, lr, path);
+    constexpr int wpb = kVitBlock / kVitWave;
+    hipLaunchKernelGGL(fn, dim3((unsigned)((n.nvw + wpb - 1) / wpb)), dim3(kVitBlock),
+                       a.lds ? embed_emis_bytes(K, W, N) : 0, c->stream, a);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipMemcpyAsync(logp_out, c->vit.d_logp, sizeof(double) * (size_t)c->R, hipMemcpyDeviceToHost, c->stream));
+    if (path && total > 0)
+        HIP_TRY(hipMemcpyAsync(path_out, n.d_path, sizeof(int32_t) * (size_t)total, hipMemcpyDeviceToHost, c->stream));
+    if (bounds_out && n_pos > 0)
+        HIP_TRY(hipMemcpyAsync(bounds_out, n.d_bounds, sizeof(int32_t) * (size_t)n_pos, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    return HMMBW_OK;
+}

@@ -260,6 +260,7 @@ static void free_obs(hmmbw_ctx *c) {
     viterbi_free(c);
     posterior_free(c);
     wordnet_free(c);
+    align_free(c);
     c->wq_grid = 0;
     c->has_obs = false;
 }

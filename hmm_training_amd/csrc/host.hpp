@@ -3,7 +3,8 @@
 // cross units.  Owners: alloc.hip (block cache, ledger), peer.hip (peer all-reduce), comm.hip (RCCL),
 // group.hip (grouped launches), viterbi.hip (hmmbw_viterbi and its kernels), posterior.hip (hmmbw_posterior and
 // its kernels), wordnet.hip (hmmbw_wordnet_decode and its kernels), embedded.hip (hmmbw_embedded_train and its
-// kernels; it keeps nothing in the context), hmmbw.hip (everything else, and the definitions of the helpers below).
+// kernels; it keeps nothing in the context), align.hip (hmmbw_align and its kernels), hmmbw.hip (everything else,
+// and the definitions of the helpers below).
 // The observation layout and the launch map hmmbw.hip plans are obs_plan.hpp's: pure, shared with the
 // kernels, tested without a GPU (tests/test_obs_plan.py).
 #pragma once
@@ -194,6 +195,20 @@ struct hmmbw_ctx {
         unsigned char *d_start = nullptr;  // with paths only: caller CSR order
         unsigned char *d_bp = nullptr;     // with paths only: rows x kWnRowBytes
     } wn;
+    // hmmbw_align (align.hip): it shares the decoder's slot_out and device logp; its own buffers are allocated on
+    // first use (the back-pointers on the first alignment with paths) and freed with the observations
+    struct Align {
+        int GW = 0;                        // the group width d_psi_off and d_bp were planned for (0: none)
+        long long rows = 0, nvw = 0;       // back-pointer rows of all decoding waves | decoding waves
+        long long *d_psi_off = nullptr;    // decoding wave -> its first back-pointer row
+        double *d_in = nullptr, *d_tab = nullptr;  // the staged bank (linear) | the log tables (align_plan.hpp)
+        long long *d_word_off = nullptr;   // [R + 1] the transcripts, CSR in caller order
+        int *d_word_ids = nullptr;
+        size_t n_in = 0, n_tab = 0, n_ids = 0, n_bounds = 0;  // lengths in elements
+        int32_t *d_path = nullptr;         // with paths only: caller CSR order of the observations
+        int32_t *d_bounds = nullptr;       // with paths only: caller CSR order of the transcripts
+        unsigned *d_bp = nullptr;          // with paths only: rows x 64 lanes
+    } al;
     // native RCCL communicator (hmmbw_comm_init): the multi-rank hmmbw_iterate all-reduces d_ext
     ncclComm_t comm = nullptr;
     double *d_ext = nullptr;      // non-fused multi-rank paths: the packed statistics to all-reduce
@@ -312,6 +327,9 @@ void posterior_free(hmmbw_ctx *c);  // hmmbw_posterior's buffers; callers synchr
 
 // wordnet.hip
 void wordnet_free(hmmbw_ctx *c);  // hmmbw_wordnet_decode's buffers; callers synchronise the context first
+
+// align.hip
+void align_free(hmmbw_ctx *c);  // hmmbw_align's buffers; callers synchronise the context first
 
 // peer.hip
 std::string peer_off_msg(const hmmbw_ctx *c);

@@ -27,8 +27,8 @@ import torch
 
 from ._lib import (ALLREDUCE, INFO_WIDE_WQ_ACTIVE, OPT_ALLREDUCE, OPT_DETERMINISTIC, OPT_LIVE_STATUS, OPT_MERGE_MSTEP,
                    OPT_PEER_TIMEOUT_MS, OPT_SAFE_SCALING, OPT_STAT_COPIES, OPT_WIDE_WQ, OPT_WQ_TIMEOUT_MS, TOPOLOGY,
-                   TOPOLOGY_NAME, WORDNET_DENSE, WORDNET_END_FINAL, EMBED_DENSE, EMBED_END_FINAL, IterRecord, Status,
-                   check, lib)
+                   TOPOLOGY_NAME, WORDNET_DENSE, WORDNET_END_FINAL, EMBED_DENSE, EMBED_END_FINAL, ALIGN_DENSE, ALIGN_END_FINAL,
+                   IterRecord, Status, check, lib)
 
 IterCallback = Callable[[int, float, float], None]
 
@@ -652,6 +652,47 @@ class BaumWelchEngine:
             max(max_iterations, 1), ctypes.byref(n), logp.ctypes.data))
         records = [(recs[i].log_likelihood, recs[i].diff) for i in range(n.value)]
         return pi, A, B, records, logp[: self.n_seq]
+
+    def align(self, pi, A, B, transcripts, end_final: bool = False, dense: bool = False, paths: bool = True):
+        """Forced alignment of every loaded sequence to its transcript through a bank of W word models of the
+        engine's shape (hmmbw_align): (paths, bounds, logp).  pi [W, N], A [W, N, N], B [W, N, M]; transcripts[r]
+        lists the word ids spoken in sequence r, in order.  paths: one int32 array of composite states l N + j per
+        sequence, l the transcript position; bounds: one int32 array per sequence, the first frame of every
+        position (position l ends where l + 1 starts, the last one at T); both all -1 where logp is -inf, and both
+        None with paths=False (scores only).  logp: the best path's log-probability.  end_final: the path ends in
+        the last state of the last word; dense: the dense within-word scan even for a left-to-right bank.  Needs
+        observations only: the engine's own parameters and training state are neither read nor changed."""
+        pi = np.ascontiguousarray(pi, dtype=np.float64)
+        if pi.ndim != 2 or pi.shape[1] != self.N:
+            raise ValueError(f"pi must be [W, {self.N}], not {pi.shape}")
+        W = pi.shape[0]
+        A = np.ascontiguousarray(A, dtype=np.float64)
+        B = np.ascontiguousarray(B, dtype=np.float64)
+        if A.shape != (W, self.N, self.N) or B.shape != (W, self.N, self.M):
+            raise ValueError(f"A must be [{W}, {self.N}, {self.N}] and B [{W}, {self.N}, {self.M}], "
+                             f"not {A.shape} and {B.shape}")
+        if len(transcripts) != self.n_seq:
+            raise ValueError(f"{len(transcripts)} transcripts for {self.n_seq} loaded sequences")
+        off = np.zeros(len(transcripts) + 1, dtype=np.int64)
+        np.cumsum([len(t) for t in transcripts], out=off[1:])
+        n_pos = int(off[-1])
+        ids = np.zeros(max(n_pos, 1), dtype=np.int32)
+        if n_pos:
+            ids[:n_pos] = np.concatenate([np.asarray(t, dtype=np.int64).reshape(-1) for t in transcripts])
+        flags = (ALIGN_END_FINAL if end_final else 0) | (ALIGN_DENSE if dense else 0)
+        logp = np.zeros(max(self.n_seq, 1))
+        total = getattr(self, "n_symbols_total", 0)
+        flat = np.zeros(max(total, 1), dtype=np.int32) if paths else None
+        first = np.zeros(max(n_pos, 1), dtype=np.int32) if paths else None
+        check(self._lib.hmmbw_align(
+            self._ctx, W, pi.ctypes.data, A.ctypes.data, B.ctypes.data, off.ctypes.data, ids.ctypes.data, self.n_seq,
+            flags, logp.ctypes.data, flat.ctypes.data if paths else None, total,
+            first.ctypes.data if paths else None, n_pos))
+        if not paths:
+            return None, None, logp[: self.n_seq]
+        if not self.n_seq:
+            return [], [], logp[:0]
+        return np.split(flat[:total], self._offsets[1:-1]), np.split(first[:n_pos], off[1:-1]), logp[: self.n_seq]
 
     def timing(self, enable: int = -1) -> Tuple[float, int]:
         """(accumulated E-step ms, timed launches) of hmmbw_timing; enable >= 0 also resets and sets the

@@ -13,7 +13,7 @@ import numpy as np
 
 from .engine import BaumWelchEngine, EngineGroup
 from .hmm_classes import HMMTrained
-from .hmm_training import get_observations
+from .hmm_training import get_observations, transcript_ids
 
 
 def score_matrix(observations: Sequence[np.ndarray], models: Sequence[HMMTrained], device=None) -> np.ndarray:
@@ -118,6 +118,42 @@ def decode_words(observations: Sequence[np.ndarray], models: Sequence[HMMTrained
         eng.set_observations(observations)
         paths, starts, logp = eng.wordnet_decode(pi, A, B, word_init, word_trans, end_final=end_final)
     return [segments_from_path(p, s, N, words) for p, s in zip(paths, starts)], logp
+
+
+def align_words(observations: Sequence[np.ndarray], transcripts: Sequence[Sequence], models: Sequence[HMMTrained],
+                end_final: bool = True, device=None) -> Tuple[List[List[Tuple[object, int, int]]], np.ndarray]:
+    """(segments, logp): where each word of a known utterance lies: the best path of every recording through the
+    chain of the word models its transcript names, all sequences in one launch (BaumWelchEngine.align).
+    transcripts[r] lists the models' .word names spoken in recording r, as train_connected takes them.  segments[r]
+    lists (word, start_frame, end_frame_exclusive), one per transcript position, in order; it is [] where no path
+    explains the recording (logp -inf; a recording shorter than its transcript is one).  end_final: every
+    recording ends in the last state of its last word, as train_connected and decode_words assume by default.  The
+    models must share one shape."""
+    if len(models) == 0:
+        raise ValueError("no word models")
+    N, M = int(models[0].states), int(np.asarray(models[0].B).shape[1])
+    for hmm in models:
+        if int(hmm.states) != N or np.asarray(hmm.B).shape != (N, M) or np.asarray(hmm.A).shape != (N, N):
+            raise ValueError("forced alignment needs word models of one shape (N states, M symbols)")
+    if len(transcripts) != len(observations):
+        raise ValueError(f"{len(transcripts)} transcripts for {len(observations)} recordings")
+    ids = transcript_ids(transcripts, models)
+    if len(observations) == 0:
+        return [], np.zeros(0)
+    pi = np.stack([np.asarray(h.Pi, dtype=np.float64).reshape(N) for h in models])
+    A = np.stack([np.asarray(h.A, dtype=np.float64) for h in models])
+    B = np.stack([np.asarray(h.B, dtype=np.float64) for h in models])
+    with BaumWelchEngine(N, M, device=device) as eng:
+        eng.set_observations(list(observations))
+        _, bounds, logp = eng.align(pi, A, B, ids, end_final=end_final)
+    segments = []
+    for r, (b, words) in enumerate(zip(bounds, ids)):
+        if logp[r] == -np.inf:
+            segments.append([])
+            continue
+        ends = np.append(b[1:], len(observations[r]))
+        segments.append([(models[w].word, int(s), int(e)) for w, s, e in zip(words, b, ends)])
+    return segments, logp
 
 
 def calculate_log_likelihood(recording_observations: np.ndarray, hmm: HMMTrained) -> float:

@@ -336,6 +336,18 @@ def hmm_training_group(observation_sets: Sequence[List[np.ndarray]], N: int = 4,
     return results
 
 
+def transcript_ids(transcripts: Sequence[Sequence], models: Sequence[HMMTrained]) -> List[List[int]]:
+    """Transcripts of the models' .word names as lists of indices into models (train_connected, align_words)."""
+    index = {h.word: w for w, h in enumerate(models)}
+    ids = []
+    for r, words in enumerate(transcripts):
+        for name in words:
+            if name not in index:
+                raise ValueError(f"transcript {r} names the word {name!r}, which no model carries")
+        ids.append([index[name] for name in words])
+    return ids
+
+
 def train_connected(observations: Sequence[np.ndarray], transcripts: Sequence[Sequence], models: Sequence[HMMTrained],
                     epsilon: float = 1e-6, max_iterations: int = 100, end_final: bool = True, *,
                     device: Optional[int] = None) -> Tuple[List[HMMTrained], List[Tuple[float, float]]]:
@@ -352,13 +364,7 @@ def train_connected(observations: Sequence[np.ndarray], transcripts: Sequence[Se
             raise ValueError("embedded training needs word models of one shape (N states, M symbols)")
     if len(transcripts) != len(observations):
         raise ValueError(f"{len(transcripts)} transcripts for {len(observations)} recordings")
-    index = {h.word: w for w, h in enumerate(models)}
-    ids = []
-    for r, words in enumerate(transcripts):
-        for name in words:
-            if name not in index:
-                raise ValueError(f"transcript {r} names the word {name!r}, which no model carries")
-        ids.append([index[name] for name in words])
+    ids = transcript_ids(transcripts, models)
     if len(observations) == 0:
         return list(models), []
     pi = np.stack([np.asarray(h.Pi, dtype=np.float64).reshape(N) for h in models])

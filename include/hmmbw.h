@@ -45,7 +45,8 @@ extern "C" {
                                  5: an older library lacks the symbol; hmmbw_embedded_train is a new entry point
                                  of version 5: an older library lacks the symbol; hmmbw_mfcc and
                                  hmmbw_mfcc_tables are new entry points of version 5: an older library lacks the
-                                 symbols) */
+                                 symbols; hmmbw_align is a new entry point of version 5: an older library lacks
+                                 the symbol) */
 
 #define HMMBW_OK 0
 #define HMMBW_E_INVALID (-1)        /* bad argument (shape, range, null pointer)             */
@@ -354,6 +355,46 @@ int hmmbw_embedded_train(hmmbw_ctx *ctx, int n_words,
                          int flags, double epsilon, int64_t max_iterations, int normalise,
                          hmmbw_iter_record *records, int64_t records_cap, int64_t *n_records,
                          double *logp_out);
+
+/* SYNC. Forced alignment of the loaded sequences to their transcripts: the Viterbi path of utterance r through the
+ * chain of the word models word_ids[word_offsets[r] .. word_offsets[r+1]) names, the hard-decision counterpart of
+ * hmmbw_embedded_train on exactly the same chain, log domain, fp64.  The bank and the transcripts are given as for
+ * hmmbw_embedded_train: HOST linear doubles pi [W][N], A [W][N][N], B [W][N][M], not necessarily normalised; CSR
+ * transcripts in caller order, a word may repeat, immediately too.  Composite state (l, j) for transcript position
+ * l and state j has index l N + j; log 0 = -inf:
+ *   delta_0(0,j)  = log pi_{w_0}[j] + log b_{w_0,j}(o_0);   delta_0(l>0, .) = -inf
+ *   inner_t(l,j)  = max_i delta_{t-1}(l,i) + log a_{w_l}[i][j]     the SMALLEST i on ties (strict '>' scan from 0)
+ *   entry_t(l,j)  = delta_{t-1}(l-1,N-1) + log pi_{w_l}[j]         -inf for l = 0
+ *   delta_t(l,j)  = (entry_t > inner_t ? entry_t : inner_t) + log b_{w_l,j}(o_t)   the within-word arc wins ties
+ * End state: the smallest j attaining max_j delta_{T-1}(L-1, j); with HMMBW_ALIGN_END_FINAL only (L-1, N-1)
+ * competes.  Every instance takes at least one frame, so an utterance with T < L has no path.
+ * HMMBW_ALIGN_DENSE forces the dense within-word scan even if every A of the bank is left-to-right.
+ * logp_out[r] (R doubles, caller order, required): the best path's log-probability, -inf if no complete path has
+ * positive probability.  path_out (may be NULL: scores only, no back-pointers are stored): int32, caller CSR order
+ * of the observations, path_out[offsets[r] + t] = l N + j; path_len must equal the total number of loaded symbols,
+ * checked whether or not path_out is NULL.  bounds_out (may be NULL; only together with path_out): int32, caller
+ * CSR order of the transcripts, bounds_out[word_offsets[r] + l] = the first frame of instance l: 0 for l = 0, else
+ * the frame whose step took the entry arc into l; instance l ends where l + 1 starts, the last one at T.
+ * bounds_len must equal word_offsets[n_seq], checked either way.  A sequence whose logp is -inf has path -1 and
+ * bounds -1 throughout.  No NaN anywhere.  Nothing is summed atomically: two calls return identical bytes, and a
+ * context in deterministic mode is accepted.
+ * HMMBW_E_INVALID: n_words < 1, a NULL bank, transcript or logp_out pointer, bounds_out without path_out, n_seq
+ * different from the loaded count, a wrong path_len or bounds_len, an empty transcript, a word id outside [0, W),
+ * offsets that do not start at 0 or decrease, a negative, infinite or NaN bank parameter, unknown flag bits.
+ * HMMBW_E_UNSUPPORTED: n_words > 64, a transcript longer than 64 words, a context of N > 8.  HMMBW_E_STATE: no
+ * observations loaded, or an iteration is open (hmmbw_iterate_begin).  HMMBW_E_HIP: the back-pointer workspace (256
+ * bytes per step and wave of 64 / GW utterances, GW the smallest of 8, 16, 32, 64 that holds the longest
+ * transcript) could not be allocated; the message names its size.
+ * Needs loaded observations only: it neither reads nor changes the context's parameters, statistics,
+ * hmmbw_get_loglik values or training state.  A multi-rank context aligns its own shard, no collective. */
+#define HMMBW_ALIGN_END_FINAL 1
+#define HMMBW_ALIGN_DENSE     2   /* force the dense within-word scan even if every A is left-to-right */
+int hmmbw_align(hmmbw_ctx *ctx, int n_words,
+                const double *pi, const double *A, const double *B,
+                const int64_t *word_offsets, const int32_t *word_ids, int64_t n_seq,
+                int flags,
+                double *logp_out, int32_t *path_out, int64_t path_len,
+                int32_t *bounds_out, int64_t bounds_len);
 
 /* Engine knobs.  HMMBW_OPT_SAFE_SCALING = 1 forces the per-step power-of-two normalisation of the
  * forward recursion (default 0: lagged normalisation, automatic per-wave fallback to the per-step
