@@ -6,7 +6,8 @@ alloc.hip: block cache and allocation ledger; peer.hip: peer all-reduce; comm.hi
 group.hip: grouped launches; viterbi.hip: the Viterbi decoder and its kernels; posterior.hip: the state
 posteriors and their kernels; lbg.hip: LBG codebook training and its kernels; wordnet.hip: connected-word
 decoding and its kernels; embedded.hip: embedded training over transcribed word sequences and its kernels;
-mfcc.hip: the MFCC front end and its kernel; align.hip: forced alignment to a transcript and its kernels), the VQ
+mfcc.hip: the MFCC front end and its kernel; align.hip: forced alignment to a transcript and its kernels; what
+wordnet.hip, embedded.hip and align.hip share is csrc/word_units.hpp, a header and no unit of its own), the VQ
 encoder (csrc/vq.hip), one small-N E-step instantiation unit per
 state count N = 1..16 (csrc/estep_small_inst.hip with -DHMMBW_INST_N=n) and the wide-N unit
 (csrc/estep_wide_inst.hip).

@@ -22,9 +22,8 @@
 // predecessor and the entry-arc bit), one coalesced 256-byte row per step and wave; the backtrace runs in the same
 // kernel and loads eight steps' rows at a time, so the dependent step is a cross-lane pick from lane l, never a
 // memory access.  Lanes past the transcript's end and padding slots hold -inf throughout and write nothing.
-#include "host.hpp"
+#include "word_units.hpp"
 #include "align_plan.hpp"
-#include "lane_ops.hpp"
 
 namespace hmmbw {
 
@@ -54,46 +53,8 @@ __global__ void __launch_bounds__(256) k_align_prep(const double *__restrict__ i
                                                     double *__restrict__ tab) {
     const int NP = embed_np(N);
     const double *pi = in, *A = pi + (long long)W * N, *B = A + (long long)W * N * N;
-    for (long long e = (long long)blockIdx.x * blockDim.x + threadIdx.x; e < o.total; e += (long long)gridDim.x * blockDim.x) {
-        double v = 0.0;  // log 0 = -inf below
-        if (e < o.A) {
-            const int w = (int)(e / NP), j = (int)(e % NP);
-            if (j < N) v = pi[w * N + j];
-        } else if (e < o.B) {
-            if (e - o.A < (long long)W * N * N) v = A[e - o.A];
-        } else {
-            const long long x = e - o.B;
-            const long long k = x / ((long long)W * NP);
-            const int w = (int)(x / NP % W), j = (int)(x % NP);
-            if (j < N) v = B[((long long)w * N + j) * K + k];
-        }
-        tab[e] = log(v);
-    }
-}
-
-// the value of lane l - 1 of the group, -inf at the group's left edge
-template <int GW>
-__device__ __forceinline__ double al_from_left(double x, int l) {
-    double nb;
-    if constexpr (GW <= 16) nb = dpp<0x111>(x);  // row_shr:1
-    else nb = __shfl_up(x, 1, GW);
-    return l > 0 ? nb : -INFINITY;
-}
-
-// a lane's N values of one table row (NP doubles, 16-B aligned when NP >= 2)
-template <int N>
-__device__ __forceinline__ void al_load_row(const double *p, double (&r)[N]) {
-    if constexpr (N == 1) {
-        r[0] = p[0];
-    } else {
-        const double2 *p2 = reinterpret_cast<const double2 *>(p);
-#pragma unroll
-        for (int h = 0; h < (N + 1) / 2; ++h) {
-            const double2 x = p2[h];
-            r[2 * h] = x.x;
-            if (2 * h + 1 < N) r[2 * h + 1] = x.y;
-        }
-    }
+    for (long long e = (long long)blockIdx.x * blockDim.x + threadIdx.x; e < o.total; e += (long long)gridDim.x * blockDim.x)
+        tab[e] = log(embed_bank_value(pi, A, B, W, N, NP, K, o, e));  // log 0 = -inf in the padding
 }
 
 template <int GW, int N, bool LR, bool PATH>
@@ -159,7 +120,7 @@ __global__ void __launch_bounds__(kVitBlock) k_align(AlArgs a) {
         }
     }
     double lpi[N];
-    al_load_row<N>(a.tab + wrow, lpi);
+    load_row<N>(a.tab + wrow, lpi);
 #pragma unroll
     for (int j = 0; j < N; ++j) lpi[j] = live ? lpi[j] : -INFINITY;
     unsigned *bp = nullptr;
@@ -171,7 +132,7 @@ __global__ void __launch_bounds__(kVitBlock) k_align(AlArgs a) {
 
     uint4 qn = chunk(0);
     double lbn[N];  // the next step's emissions
-    al_load_row<N>(row_of(qn.x & 0xffffu), lbn);
+    load_row<N>(row_of(qn.x & 0xffffu), lbn);
     for (int t0 = 0; t0 < Tw; t0 += kChunk) {
         const uint4 q = qn;
         qn = chunk(t0 + kChunk);
@@ -185,7 +146,7 @@ __global__ void __launch_bounds__(kVitBlock) k_align(AlArgs a) {
             {
                 const int kn = k + 1;
                 const unsigned long long word = kn < 4 ? qlo : kn < 8 ? qhi : (unsigned long long)qn.x;
-                al_load_row<N>(row_of((unsigned)(word >> (16 * (kn & 3))) & 0xffffu), lbn);
+                load_row<N>(row_of((unsigned)(word >> (16 * (kn & 3))) & 0xffffu), lbn);
             }
             double nd[N];
             unsigned nib = 0;
@@ -193,7 +154,7 @@ __global__ void __launch_bounds__(kVitBlock) k_align(AlArgs a) {
 #pragma unroll
                 for (int j = 0; j < N; ++j) nd[j] = l == 0 ? lpi[j] + lb[j] : -INFINITY;
             } else {
-                const double left = al_from_left<GW>(d[N - 1], l);
+                const double left = from_left<GW>(d[N - 1], l, -INFINITY);
 #pragma unroll
                 for (int j = 0; j < N; ++j) {
                     double best;
@@ -279,33 +240,12 @@ __global__ void __launch_bounds__(kVitBlock) k_align(AlArgs a) {
 
 using AlFn = void (*)(AlArgs);
 
-template <int GW, int N>
-static AlFn al_kernel3(bool lr, bool path) {
-    if (lr) return path ? k_align<GW, N, true, true> : k_align<GW, N, true, false>;
-    return path ? k_align<GW, N, false, true> : k_align<GW, N, false, false>;
-}
-
-template <int GW>
-static AlFn al_kernel2(int N, bool lr, bool path) {
-    switch (N) {
-        case 1: return al_kernel3<GW, 1>(lr, path);
-        case 2: return al_kernel3<GW, 2>(lr, path);
-        case 3: return al_kernel3<GW, 3>(lr, path);
-        case 4: return al_kernel3<GW, 4>(lr, path);
-        case 5: return al_kernel3<GW, 5>(lr, path);
-        case 6: return al_kernel3<GW, 6>(lr, path);
-        case 7: return al_kernel3<GW, 7>(lr, path);
-        default: return al_kernel3<GW, 8>(lr, path);
-    }
-}
-
 static AlFn al_kernel(int GW, int N, bool lr, bool path) {
-    switch (GW) {
-        case 8: return al_kernel2<8>(N, lr, path);
-        case 16: return al_kernel2<16>(N, lr, path);
-        case 32: return al_kernel2<32>(N, lr, path);
-        default: return al_kernel2<64>(N, lr, path);
-    }
+    return pick_gw_n(GW, N, [=](auto gw, auto n) -> AlFn {
+        constexpr int G = decltype(gw)::value, S = decltype(n)::value;
+        if (lr) return path ? k_align<G, S, true, true> : k_align<G, S, true, false>;
+        return path ? k_align<G, S, false, true> : k_align<G, S, false, false>;
+    });
 }
 
 void align_free(hmmbw_ctx *c) {
@@ -315,50 +255,29 @@ void align_free(hmmbw_ctx *c) {
     n = hmmbw_ctx::Align{};
 }
 
-// a buffer of at least n elements: kept while it is large enough
-template <class T>
-static int al_grow(hmmbw_ctx *c, T *&p, size_t &have, size_t n) {
-    if (p && have >= n) return HMMBW_OK;
-    sync_ctx(c);
-    dfree(p);
-    have = 0;
-    if (int rc = dalloc(&p, n)) return rc;
-    have = n;
-    return HMMBW_OK;
-}
-
-// the aligner's buffers for the loaded observations, this bank shape and these transcripts: the back-pointer row
-// offsets of the group width, the staging and table buffers, the transcripts, and with paths the path, the bounds
-// and the back-pointers
+// the aligner's buffers for the loaded observations, this bank shape and these transcripts: what
+// word_decode_buffers keeps, the transcripts, and with paths the path, the bounds and the back-pointers
 static int align_buffers(hmmbw_ctx *c, int GW, size_t n_in, size_t n_tab, size_t n_pos, bool path) {
-    if (int rc = viterbi_plan_ready(c)) return rc;  // slot_out and the device logp
     hmmbw_ctx::Align &n = c->al;
-    if (n.GW != GW) {
-        sync_ctx(c);
-        dfree(n.d_psi_off);
-        dfree(n.d_bp);
-        n.GW = 0;
-        ViterbiPlan P = plan_viterbi_group(c->h_slen, c->h_sseq, c->R, GW);
-        if (int rc = dalloc(&n.d_psi_off, P.psi_off.size())) return rc;
-        if (!P.psi_off.empty())
-            HIP_TRY(hipMemcpy(n.d_psi_off, P.psi_off.data(), sizeof(long long) * P.psi_off.size(), hipMemcpyHostToDevice));
-        n.rows = P.psi_rows;
-        n.nvw = P.nvw;
-        n.GW = GW;
-    }
-    if (int rc = al_grow(c, n.d_in, n.n_in, n_in)) return rc;
-    if (int rc = al_grow(c, n.d_tab, n.n_tab, n_tab)) return rc;
-    if (int rc = al_grow(c, n.d_word_ids, n.n_ids, n_pos)) return rc;
+    if (int rc = word_decode_buffers(c, n, GW, n_in, n_tab)) return rc;
+    if (int rc = grow(c, n.d_word_ids, n.n_ids, n_pos)) return rc;
     if (!n.d_word_off)
         if (int rc = dalloc(&n.d_word_off, (size_t)c->R + 1)) return rc;
     if (path) {
-        int rc = al_grow(c, n.d_bounds, n.n_bounds, n_pos);
+        int rc = grow(c, n.d_bounds, n.n_bounds, n_pos);
         if (!rc && !n.d_path) rc = dalloc(&n.d_path, (size_t)c->vit.plan.total);
-        if (rc) return rc;
-        if (!n.d_bp)
-            if (int rc2 = dalloc(&n.d_bp, (size_t)n.rows * kVitWave))
-                return fail(rc2, "the alignment back-pointers (" + std::to_string(align_bp_bytes(n.rows)) +
-                                     " bytes) do not fit: " + g_err);
+        const bool bp = !rc && !n.d_bp;  // the failure is the back-pointers'
+        if (bp) rc = dalloc(&n.d_bp, (size_t)n.rows * kVitWave);
+        if (rc) {  // none of the three is kept: the next call with paths allocates them again
+            sync_ctx(c);
+            dfree(n.d_bounds);
+            n.n_bounds = 0;
+            dfree(n.d_path);
+            dfree(n.d_bp);
+            if (!bp) return rc;
+            return fail(rc, "the alignment back-pointers (" + std::to_string(align_bp_bytes(n.rows)) +
+                                " bytes) do not fit: " + g_err);
+        }
     }
     return HMMBW_OK;
 }
@@ -372,43 +291,22 @@ extern "C" int hmmbw_align(hmmbw_ctx *c, int n_words, const double *pi, const do
     if (!c) return fail(HMMBW_E_INVALID, "null context");
     if (!c->has_obs) return fail(HMMBW_E_STATE, "observations not set");
     if (int rc = set_device(c)) return rc;
-    if (n_words < 1) return fail(HMMBW_E_INVALID, "n_words " + std::to_string(n_words) + " < 1");
     if (!pi || !A || !B || !word_offsets || !word_ids || !logp_out) return fail(HMMBW_E_INVALID, "null argument");
     if (bounds_out && !path_out) return fail(HMMBW_E_INVALID, "bounds_out needs path_out");
     if (!align_flags_ok(flags)) return fail(HMMBW_E_INVALID, "unknown flag");
-    if (n_seq != c->R)
-        return fail(HMMBW_E_INVALID, "n_seq " + std::to_string(n_seq) + " is not the number of loaded sequences (" +
-                                         std::to_string(c->R) + ")");
-    if (n_words > kAlMaxWords)
-        return fail(HMMBW_E_UNSUPPORTED, "n_words " + std::to_string(n_words) + " > " + std::to_string(kAlMaxWords));
-    if (c->N > kAlMaxStates)
-        return fail(HMMBW_E_UNSUPPORTED, "word models of N " + std::to_string(c->N) + " > " + std::to_string(kAlMaxStates) + " states");
+    if (int rc = check_n_seq(c, n_seq)) return rc;
+    if (int rc = check_word_bank(c, n_words, pi, A, B, kAlMaxWords, kAlMaxStates, "a negative, infinite or NaN bank parameter"))
+        return rc;
     const int W = n_words, N = c->N, K = c->K;
-    if (!wordnet_weights_ok(pi, (long long)W * N) || !wordnet_weights_ok(A, (long long)W * N * N) ||
-        !wordnet_weights_ok(B, (long long)W * N * K))
-        return fail(HMMBW_E_INVALID, "a negative, infinite or NaN bank parameter");
     long long longest = 0;
-    switch (embed_transcripts_check(word_offsets, word_ids, n_seq, W, &longest, nullptr)) {
-        case 0: break;
-        case 1: return fail(HMMBW_E_INVALID, "an empty transcript");
-        case 2: return fail(HMMBW_E_INVALID, "a word id outside [0, " + std::to_string(W) + ")");
-        default: return fail(HMMBW_E_INVALID, "word_offsets do not start at 0 or decrease");
-    }
-    if (longest > kAlMaxWords)
-        return fail(HMMBW_E_UNSUPPORTED, "a transcript of " + std::to_string(longest) + " words > " + std::to_string(kAlMaxWords));
+    if (int rc = check_transcripts(word_offsets, word_ids, n_seq, W, kAlMaxWords, &longest, nullptr)) return rc;
     if (int rc = check_closed(c)) return rc;
     long long total = 0;
-    for (int T : c->h_slen) total += T;
+    if (int rc = check_path_len(c, path_len, &total)) return rc;
     const long long n_pos = n_seq > 0 ? word_offsets[n_seq] : 0;
-    switch (align_lengths_check(path_len, total, bounds_len, n_pos)) {
-        case 0: break;
-        case 1:
-            return fail(HMMBW_E_INVALID, "path_len " + std::to_string(path_len) + " is not the number of loaded symbols (" +
-                                             std::to_string(total) + ")");
-        default:
-            return fail(HMMBW_E_INVALID, "bounds_len " + std::to_string(bounds_len) +
-                                             " is not the number of transcript positions (" + std::to_string(n_pos) + ")");
-    }
+    if (align_lengths_check(path_len, total, bounds_len, n_pos))
+        return fail(HMMBW_E_INVALID, "bounds_len " + std::to_string(bounds_len) +
+                                         " is not the number of transcript positions (" + std::to_string(n_pos) + ")");
     if (c->R == 0) return HMMBW_OK;
 
     const bool path = path_out != nullptr;
@@ -419,29 +317,15 @@ extern "C" int hmmbw_align(hmmbw_ctx *c, int n_words, const double *pi, const do
     if (int rc = align_buffers(c, GW, (size_t)n_in, (size_t)o.total, (size_t)n_pos, path)) return rc;
     hmmbw_ctx::Align &n = c->al;
 
-    // the bank, staged as one block: pi | A | B; the transcripts as the kernel's types
-    std::vector<double> h((size_t)n_in);
-    {
-        double *hp = std::copy(pi, pi + (long long)W * N, h.data());
-        hp = std::copy(A, A + (long long)W * N * N, hp);
-        std::copy(B, B + (long long)W * N * K, hp);
-    }
-    HIP_TRY(hipMemcpy(n.d_in, h.data(), sizeof(double) * (size_t)n_in, hipMemcpyHostToDevice));
-    {
-        std::vector<long long> off(word_offsets, word_offsets + n_seq + 1);
-        std::vector<int> ids(word_ids, word_ids + n_pos);
-        HIP_TRY(hipMemcpy(n.d_word_off, off.data(), sizeof(long long) * off.size(), hipMemcpyHostToDevice));
-        HIP_TRY(hipMemcpy(n.d_word_ids, ids.data(), sizeof(int) * ids.size(), hipMemcpyHostToDevice));
-    }
+    std::vector<double> h;
+    if (int rc = stage_bank(n.d_in, h, n_in, pi, A, B, W, N, K)) return rc;
+    if (int rc = upload_transcripts(n.d_word_off, n.d_word_ids, word_offsets, word_ids, n_seq, n_pos)) return rc;
     hipLaunchKernelGGL(k_align_prep, dim3((unsigned)std::min<long long>((o.total + 255) / 256, 1024)), dim3(256), 0,
                        c->stream, (const double *)n.d_in, W, N, K, o, n.d_tab);
     HIP_TRY(hipGetLastError());
 
     AlArgs a{};
-    a.sym = c->d_sym;  // never d_sym2: the row tables' packs (or symbol ids)
-    a.wave_symoff = c->d_wsym;
-    a.slot_len = c->d_slen;
-    a.slot_seq = c->d_sseq;
+    fill_slot_args(c, a);
     a.slot_out = c->vit.d_slot_out;
     a.psi_off = n.d_psi_off;
     a.word_off = n.d_word_off;
@@ -451,15 +335,9 @@ extern "C" int hmmbw_align(hmmbw_ctx *c, int n_words, const double *pi, const do
     a.logp = c->vit.d_logp;
     a.path = path ? n.d_path : nullptr;
     a.bounds = path ? n.d_bounds : nullptr;
-    a.nslots = c->vit.plan.nslots;
     a.o_A = o.A;
     a.o_B = o.B;
-    a.U = c->U;
     a.W = W;
-    a.K = K;
-    const long long div = viterbi_pack_div(c->lds_tables(), c->G, 0);  // rows of G entries, no pad column
-    a.div = (int)div;
-    a.shift = viterbi_pack_shift(div);
     a.lds = embed_emis_in_lds(K, W, N) ? 1 : 0;
     a.end_final = (flags & HMMBW_ALIGN_END_FINAL) ? 1 : 0;
     const AlFn fn = al_kernel(GW, N, lr, path);

@@ -31,9 +31,7 @@
 // k_embed_conv (one workgroup) forms L = LSE_r log P_r, writes the iteration's record and sets done, after which
 // every later launch of the three returns at once.  The host enqueues kEmChunk iterations between two reads of the
 // state.
-#include "host.hpp"
-#include "embed_plan.hpp"
-#include "lane_ops.hpp"
+#include "word_units.hpp"
 #include "mstep.hpp"  // the element formulas of the M-step
 
 namespace hmmbw {
@@ -68,21 +66,7 @@ __global__ void __launch_bounds__(256) k_embed_prep(const double *__restrict__ i
     const int NP = embed_np(N);
     const double *pi = in, *A = pi + (long long)W * N, *B = A + (long long)W * N * N;
     const long long stride = (long long)gridDim.x * blockDim.x, first = (long long)blockIdx.x * blockDim.x + threadIdx.x;
-    for (long long e = first; e < o.total; e += stride) {
-        double v = 0.0;
-        if (e < o.A) {
-            const int w = (int)(e / NP), j = (int)(e % NP);
-            if (j < N) v = pi[w * N + j];
-        } else if (e < o.B) {
-            if (e - o.A < (long long)W * N * N) v = A[e - o.A];
-        } else {
-            const long long x = e - o.B;
-            const long long k = x / ((long long)W * NP);
-            const int w = (int)(x / NP % W), j = (int)(x % NP);
-            if (j < N) v = B[((long long)w * N + j) * K + k];
-        }
-        tab[e] = v;
-    }
+    for (long long e = first; e < o.total; e += stride) tab[e] = embed_bank_value(pi, A, B, W, N, NP, K, o, e);
     for (long long e = first; e < nstats; e += stride) stats[e] = 0.0;
     if (first == 0) {
         EmbedState s{};
@@ -92,38 +76,6 @@ __global__ void __launch_bounds__(256) k_embed_prep(const double *__restrict__ i
         s.epsilon = epsilon;
         s.max_iterations = max_iterations;
         *state = s;
-    }
-}
-
-// the value of lane l - 1 / l + 1 of the group, 0 at the group's edge
-template <int GW>
-__device__ __forceinline__ double from_left(double x, int l) {
-    double nb;
-    if constexpr (GW <= 16) nb = dpp<0x111>(x);  // row_shr:1
-    else nb = __shfl_up(x, 1, GW);
-    return l > 0 ? nb : 0.0;
-}
-template <int GW>
-__device__ __forceinline__ double from_right(double x, int l) {
-    double nb;
-    if constexpr (GW <= 16) nb = dpp<0x101>(x);  // row_shl:1
-    else nb = __shfl_down(x, 1, GW);
-    return l < GW - 1 ? nb : 0.0;
-}
-
-// a lane's N values of one table row (NP doubles, 16-B aligned when NP >= 2)
-template <int N>
-__device__ __forceinline__ void em_load_row(const double *p, double (&r)[N]) {
-    if constexpr (N == 1) {
-        r[0] = p[0];
-    } else {
-        const double2 *p2 = reinterpret_cast<const double2 *>(p);
-#pragma unroll
-        for (int h = 0; h < (N + 1) / 2; ++h) {
-            const double2 x = p2[h];
-            r[2 * h] = x.x;
-            if (2 * h + 1 < N) r[2 * h + 1] = x.y;
-        }
     }
 }
 
@@ -202,7 +154,7 @@ __global__ void __launch_bounds__(kVitBlock) k_embed_estep(EmArgs a) {
         }
     }
     double pi[N];
-    em_load_row<N>(a.tab + wrow, pi);
+    load_row<N>(a.tab + wrow, pi);
 #pragma unroll
     for (int j = 0; j < N; ++j) pi[j] = live ? pi[j] : 0.0;
 
@@ -220,8 +172,8 @@ __global__ void __launch_bounds__(kVitBlock) k_embed_estep(EmArgs a) {
             const int t = t0 + k;
             if (t >= Tw) break;  // the whole wave
             double b[N];
-            em_load_row<N>(bt + (size_t)symbol(q, k) * kstride, b);
-            const double left = from_left<GW>(al[N - 1], l);
+            load_row<N>(bt + (size_t)symbol(q, k) * kstride, b);
+            const double left = from_left<GW>(al[N - 1], l, 0.0);
             double nd[N];
 #pragma unroll
             for (int j = 0; j < N; ++j) {
@@ -278,7 +230,7 @@ __global__ void __launch_bounds__(kVitBlock) k_embed_estep(EmArgs a) {
             const bool act = t < T, last = t == T - 1;
             const unsigned o = symbol(q, k);
             double at[N], b[N];
-            em_load_row<N>(bt + (size_t)o * kstride, b);
+            load_row<N>(bt + (size_t)o * kstride, b);
 #pragma unroll
             for (int j = 0; j < N; ++j) at[j] = act ? ws[((long long)t * N + j) * kVitWave] : 0.0;
             double v[N];
@@ -288,8 +240,8 @@ __global__ void __launch_bounds__(kVitBlock) k_embed_estep(EmArgs a) {
                 v[j] = bn[j] * be[j];
                 es = fma(pi[j], v[j], es);
             }
-            const double right = from_right<GW>(es, l);
-            const double aleft = from_left<GW>(at[N - 1], l);
+            const double right = from_right<GW>(es, l, 0.0);
+            const double aleft = from_left<GW>(at[N - 1], l, 0.0);
             double bp[N];  // beta_t before its rescale
 #pragma unroll
             for (int i = 0; i < N; ++i) {
@@ -455,27 +407,11 @@ __global__ void __launch_bounds__(256) k_embed_export(const double *__restrict__
 
 using EmFn = void (*)(EmArgs);
 
-template <int GW>
-static EmFn em_kernel2(int N, bool lr) {
-    switch (N) {
-        case 1: return lr ? k_embed_estep<GW, 1, true> : k_embed_estep<GW, 1, false>;
-        case 2: return lr ? k_embed_estep<GW, 2, true> : k_embed_estep<GW, 2, false>;
-        case 3: return lr ? k_embed_estep<GW, 3, true> : k_embed_estep<GW, 3, false>;
-        case 4: return lr ? k_embed_estep<GW, 4, true> : k_embed_estep<GW, 4, false>;
-        case 5: return lr ? k_embed_estep<GW, 5, true> : k_embed_estep<GW, 5, false>;
-        case 6: return lr ? k_embed_estep<GW, 6, true> : k_embed_estep<GW, 6, false>;
-        case 7: return lr ? k_embed_estep<GW, 7, true> : k_embed_estep<GW, 7, false>;
-        default: return lr ? k_embed_estep<GW, 8, true> : k_embed_estep<GW, 8, false>;
-    }
-}
-
 static EmFn em_kernel(int GW, int N, bool lr) {
-    switch (GW) {
-        case 8: return em_kernel2<8>(N, lr);
-        case 16: return em_kernel2<16>(N, lr);
-        case 32: return em_kernel2<32>(N, lr);
-        default: return em_kernel2<64>(N, lr);
-    }
+    return pick_gw_n(GW, N, [=](auto gw, auto n) -> EmFn {
+        constexpr int G = decltype(gw)::value, S = decltype(n)::value;
+        return lr ? k_embed_estep<G, S, true> : k_embed_estep<G, S, false>;
+    });
 }
 
 // the buffers of one call, from the library's block cache
@@ -495,8 +431,7 @@ struct EmWork {
 template <class T>
 static int to_device(T **d, const std::vector<T> &h) {
     if (int rc = dalloc(d, h.size())) return rc;
-    if (!h.empty()) HIP_TRY(hipMemcpy(*d, h.data(), sizeof(T) * h.size(), hipMemcpyHostToDevice));
-    return HMMBW_OK;
+    return upload(*d, h);
 }
 
 }  // namespace hmmbw
@@ -508,34 +443,19 @@ extern "C" int hmmbw_embedded_train(hmmbw_ctx *c, int n_words, double *pi, doubl
     if (!c) return fail(HMMBW_E_INVALID, "null context");
     if (!c->has_obs) return fail(HMMBW_E_STATE, "observations not set");
     if (int rc = set_device(c)) return rc;
-    if (n_words < 1) return fail(HMMBW_E_INVALID, "n_words " + std::to_string(n_words) + " < 1");
     if (!pi || !A || !B || !word_offsets || !word_ids) return fail(HMMBW_E_INVALID, "null argument");
     if (flags & ~(HMMBW_EMBED_END_FINAL | HMMBW_EMBED_DENSE)) return fail(HMMBW_E_INVALID, "unknown flag");
     if (max_iterations < 1) return fail(HMMBW_E_INVALID, "max_iterations " + std::to_string(max_iterations) + " < 1");
     if (!(epsilon >= 0.0)) return fail(HMMBW_E_INVALID, "epsilon is negative or NaN");
-    if (n_seq != c->R)
-        return fail(HMMBW_E_INVALID, "n_seq " + std::to_string(n_seq) + " is not the number of loaded sequences (" +
-                                         std::to_string(c->R) + ")");
-    if (n_words > kEmMaxWords)
-        return fail(HMMBW_E_UNSUPPORTED, "n_words " + std::to_string(n_words) + " > " + std::to_string(kEmMaxWords));
-    if (c->N > kEmMaxStates)
-        return fail(HMMBW_E_UNSUPPORTED, "word models of N " + std::to_string(c->N) + " > " + std::to_string(kEmMaxStates) + " states");
+    if (int rc = check_n_seq(c, n_seq)) return rc;
     if (c->world > 1) return fail(HMMBW_E_UNSUPPORTED, "embedded training on a multi-rank context");
     if (c->det) return fail(HMMBW_E_UNSUPPORTED, "embedded training in deterministic mode (its sums are floating-point atomics)");
+    if (int rc = check_word_bank(c, n_words, pi, A, B, kEmMaxWords, kEmMaxStates, "a negative, infinite or NaN bank parameter"))
+        return rc;
     const int W = n_words, N = c->N, K = c->K;
-    if (!wordnet_weights_ok(pi, (long long)W * N) || !wordnet_weights_ok(A, (long long)W * N * N) ||
-        !wordnet_weights_ok(B, (long long)W * N * K))
-        return fail(HMMBW_E_INVALID, "a negative, infinite or NaN bank parameter");
     long long longest = 0;
     std::vector<long long> count((size_t)W, 0);
-    switch (embed_transcripts_check(word_offsets, word_ids, n_seq, W, &longest, count.data())) {
-        case 0: break;
-        case 1: return fail(HMMBW_E_INVALID, "an empty transcript");
-        case 2: return fail(HMMBW_E_INVALID, "a word id outside [0, " + std::to_string(W) + ")");
-        default: return fail(HMMBW_E_INVALID, "word_offsets do not start at 0 or decrease");
-    }
-    if (longest > kEmMaxWords)
-        return fail(HMMBW_E_UNSUPPORTED, "a transcript of " + std::to_string(longest) + " words > " + std::to_string(kEmMaxWords));
+    if (int rc = check_transcripts(word_offsets, word_ids, n_seq, W, kEmMaxWords, &longest, count.data())) return rc;
     if (int rc = check_closed(c)) return rc;
     if (n_records) *n_records = 0;
     if (c->R == 0) return HMMBW_OK;
@@ -559,29 +479,19 @@ extern "C" int hmmbw_embedded_train(hmmbw_ctx *c, int n_words, double *pi, doubl
     if (int rc = dalloc(&w.state, 1)) return rc;
     if (int rc = to_device(&w.work_off, P.psi_off)) return rc;
     if (int rc = to_device(&w.count, count)) return rc;
-    {
-        std::vector<long long> off(word_offsets, word_offsets + n_seq + 1);
-        std::vector<int> ids(word_ids, word_ids + word_offsets[n_seq]);
-        if (int rc = to_device(&w.word_off, off)) return rc;
-        if (int rc = to_device(&w.word_ids, ids)) return rc;
-    }
-    std::vector<double> h((size_t)n_bank);
-    {
-        double *hp = std::copy(pi, pi + (long long)W * N, h.data());
-        hp = std::copy(A, A + (long long)W * N * N, hp);
-        std::copy(B, B + (long long)W * N * K, hp);
-    }
-    HIP_TRY(hipMemcpy(w.in, h.data(), sizeof(double) * (size_t)n_bank, hipMemcpyHostToDevice));
+    const long long n_pos = word_offsets[n_seq];
+    if (int rc = dalloc(&w.word_off, (size_t)n_seq + 1)) return rc;
+    if (int rc = dalloc(&w.word_ids, (size_t)n_pos)) return rc;
+    if (int rc = upload_transcripts(w.word_off, w.word_ids, word_offsets, word_ids, n_seq, n_pos)) return rc;
+    std::vector<double> h;  // the staged bank, and the trained one on the way back
+    if (int rc = stage_bank(w.in, h, n_bank, pi, A, B, W, N, K)) return rc;
     const long long nprep = std::max(o.total, so.total);
     hipLaunchKernelGGL(k_embed_prep, dim3((unsigned)std::min<long long>((nprep + 255) / 256, 1024)), dim3(256), 0,
                        c->stream, w.in, W, N, K, o, w.tab, w.stats, so.total, w.state, epsilon, (long long)max_iterations);
     HIP_TRY(hipGetLastError());
 
     EmArgs a{};
-    a.sym = c->d_sym;  // never d_sym2: the row tables' packs (or symbol ids)
-    a.wave_symoff = c->d_wsym;
-    a.slot_len = c->d_slen;
-    a.slot_seq = c->d_sseq;
+    fill_slot_args(c, a);
     a.work_off = w.work_off;
     a.word_off = w.word_off;
     a.word_ids = w.word_ids;
@@ -590,18 +500,12 @@ extern "C" int hmmbw_embedded_train(hmmbw_ctx *c, int n_words, double *pi, doubl
     a.work = w.work;
     a.logp = w.logp;
     a.state = w.state;
-    a.nslots = P.nslots;
     a.o_A = o.A;
     a.o_B = o.B;
     a.s_xi = so.xi;
     a.s_gall = so.gall;
     a.s_bnum = so.bnum;
-    a.U = c->U;
     a.W = W;
-    a.K = K;
-    const long long div = viterbi_pack_div(c->lds_tables(), c->G, 0);  // rows of G entries, no pad column
-    a.div = (int)div;
-    a.shift = viterbi_pack_shift(div);
     a.lds = embed_emis_in_lds(K, W, N) ? 1 : 0;
     a.end_final = (flags & HMMBW_EMBED_END_FINAL) ? 1 : 0;
     const EmFn fn = em_kernel(GW, N, lr);

@@ -4,7 +4,8 @@
 // group.hip (grouped launches), viterbi.hip (hmmbw_viterbi and its kernels), posterior.hip (hmmbw_posterior and
 // its kernels), wordnet.hip (hmmbw_wordnet_decode and its kernels), embedded.hip (hmmbw_embedded_train and its
 // kernels; it keeps nothing in the context), align.hip (hmmbw_align and its kernels), hmmbw.hip (everything else,
-// and the definitions of the helpers below).
+// and the definitions of the helpers below).  What wordnet.hip, embedded.hip and align.hip share beyond this
+// header, and the slot arguments they fill as viterbi.hip and posterior.hip do, is word_units.hpp's.
 // The observation layout and the launch map hmmbw.hip plans are obs_plan.hpp's: pure, shared with the
 // kernels, tested without a GPU (tests/test_obs_plan.py).
 #pragma once
@@ -183,29 +184,25 @@ struct hmmbw_ctx {
         double *d_scratch = nullptr;  // [total][N]: the alpha_hat -> gamma workspace of calls without gamma_dev
         int32_t *d_path = nullptr;    // with paths only: caller CSR order
     } post;
-    // hmmbw_wordnet_decode (wordnet.hip): it shares the decoder's slot_out and device logp; its own buffers are
-    // allocated on first use (the back-pointers on the first decode with paths) and freed with the observations
-    struct Wordnet {
+    // hmmbw_wordnet_decode (wordnet.hip) and hmmbw_align (align.hip): both share the decoder's slot_out and device
+    // logp; their own buffers are allocated on first use (the back-pointers on the first call with paths) and freed
+    // with the observations.  WordDecode is what the two keep alike (word_units.hpp, word_decode_buffers).
+    struct WordDecode {
         int GW = 0;                        // the group width d_psi_off and d_bp were planned for (0: none)
         long long rows = 0, nvw = 0;       // back-pointer rows of all decoding waves | decoding waves
         long long *d_psi_off = nullptr;    // decoding wave -> its first back-pointer row
-        double *d_in = nullptr, *d_tab = nullptr;  // the staged bank (linear) | the log tables (wordnet_plan.hpp)
+        double *d_in = nullptr, *d_tab = nullptr;  // the staged bank (linear) | the log tables (wordnet_plan.hpp, align_plan.hpp)
         size_t n_in = 0, n_tab = 0;        // their lengths in doubles
-        int32_t *d_path = nullptr;         // with paths only: caller CSR order
+        int32_t *d_path = nullptr;         // with paths only: caller CSR order of the observations
+    };
+    struct Wordnet : WordDecode {
         unsigned char *d_start = nullptr;  // with paths only: caller CSR order
         unsigned char *d_bp = nullptr;     // with paths only: rows x kWnRowBytes
     } wn;
-    // hmmbw_align (align.hip): it shares the decoder's slot_out and device logp; its own buffers are allocated on
-    // first use (the back-pointers on the first alignment with paths) and freed with the observations
-    struct Align {
-        int GW = 0;                        // the group width d_psi_off and d_bp were planned for (0: none)
-        long long rows = 0, nvw = 0;       // back-pointer rows of all decoding waves | decoding waves
-        long long *d_psi_off = nullptr;    // decoding wave -> its first back-pointer row
-        double *d_in = nullptr, *d_tab = nullptr;  // the staged bank (linear) | the log tables (align_plan.hpp)
+    struct Align : WordDecode {
         long long *d_word_off = nullptr;   // [R + 1] the transcripts, CSR in caller order
         int *d_word_ids = nullptr;
-        size_t n_in = 0, n_tab = 0, n_ids = 0, n_bounds = 0;  // lengths in elements
-        int32_t *d_path = nullptr;         // with paths only: caller CSR order of the observations
+        size_t n_ids = 0, n_bounds = 0;    // lengths in elements
         int32_t *d_bounds = nullptr;       // with paths only: caller CSR order of the transcripts
         unsigned *d_bp = nullptr;          // with paths only: rows x 64 lanes
     } al;

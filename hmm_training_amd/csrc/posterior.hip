@@ -15,8 +15,7 @@
 // output is the workspace: the forward writes alpha_t(j) to gamma[(out + t) N + j], the backward reads it back
 // and overwrites it with gamma_t(j); a lane re-reads only what it wrote itself, so program order suffices.  A
 // sequence whose forward reaches an all-zero alpha (P(O) = 0) gets zeros in every row and -1 in its path.
-#include "host.hpp"
-#include "lane_ops.hpp"
+#include "word_units.hpp"  // fill_slot_args, check_path_len
 
 namespace hmmbw {
 
@@ -255,10 +254,7 @@ extern "C" int hmmbw_posterior(hmmbw_ctx *c, double *gamma_dev, int64_t gamma_le
     if (!gamma_dev && !path_out && !logp_out) return fail(HMMBW_E_INVALID, "no output asked for");
     if (int rc = check_closed(c)) return rc;
     long long total = 0;
-    for (int T : c->h_slen) total += T;
-    if (path_len != total)
-        return fail(HMMBW_E_INVALID, "path_len " + std::to_string(path_len) + " is not the number of loaded symbols (" +
-                                         std::to_string(total) + ")");
+    if (int rc = check_path_len(c, path_len, &total)) return rc;
     if (gamma_len != total * c->N)
         return fail(HMMBW_E_INVALID, "gamma_len " + std::to_string(gamma_len) + " is not the number of loaded symbols x N (" +
                                          std::to_string(total * c->N) + ")");
@@ -280,22 +276,13 @@ extern "C" int hmmbw_posterior(hmmbw_ctx *c, double *gamma_dev, int64_t gamma_le
                        c->stream, c->d_pi, c->d_A, c->d_B, c->N, c->K, P.GV, p.d_tab);
     HIP_TRY(hipGetLastError());
     PArgs a{};
-    a.sym = c->d_sym;  // never d_sym2: the row tables' packs (or symbol ids)
-    a.wave_symoff = c->d_wsym;
-    a.slot_len = c->d_slen;
-    a.slot_seq = c->d_sseq;
+    fill_slot_args(c, a);
     a.slot_out = c->vit.d_slot_out;
     a.tab = p.d_tab;
     a.gamma = full ? (gamma_dev ? gamma_dev : p.d_scratch) : nullptr;
     a.logp = c->vit.d_logp;
     a.path = path ? p.d_path : nullptr;
-    a.nslots = P.nslots;
-    a.U = c->U;
     a.N = c->N;
-    a.K = c->K;
-    const long long div = viterbi_pack_div(c->lds_tables(), c->G, 0);  // rows of G entries, no pad column
-    a.div = (int)div;
-    a.shift = viterbi_pack_shift(div);
     const bool lds = viterbi_table_in_lds(c->K, P.GV);
     const bool lr = c->topo == HMMBW_TOPOLOGY_LEFT_TO_RIGHT && P.GV <= 16;
     const PostFn fn = post_kernel(P.GV, lr, full, lds);

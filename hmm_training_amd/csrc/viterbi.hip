@@ -16,8 +16,7 @@
 // coalesced 64-B row per step; the backtrace runs in the same kernel and loads eight rows at a time (their
 // addresses do not depend on the path, lane j holds psi_t(j)), so the dependent step is a cross-lane pick
 // s_{t-1} = psi_t[lane s_t], never a memory access.
-#include "host.hpp"
-#include "lane_ops.hpp"
+#include "word_units.hpp"  // fill_slot_args, check_path_len
 
 namespace hmmbw {
 
@@ -261,10 +260,7 @@ extern "C" int hmmbw_viterbi(hmmbw_ctx *c, double *logp_out, int32_t *path_out, 
     if (!logp_out) return fail(HMMBW_E_INVALID, "null argument");
     if (int rc = check_closed(c)) return rc;
     long long total = 0;
-    for (int T : c->h_slen) total += T;
-    if (path_len != total)
-        return fail(HMMBW_E_INVALID, "path_len " + std::to_string(path_len) + " is not the number of loaded symbols (" +
-                                         std::to_string(total) + ")");
+    if (int rc = check_path_len(c, path_len, &total)) return rc;
     if (int rc = flush_mstep(c)) return rc;
     if (c->R == 0) return HMMBW_OK;
     const bool path = path_out != nullptr;
@@ -276,23 +272,14 @@ extern "C" int hmmbw_viterbi(hmmbw_ctx *c, double *logp_out, int32_t *path_out, 
                        c->stream, c->d_pi, c->d_A, c->d_B, c->N, c->K, P.GV, v.d_tab);
     HIP_TRY(hipGetLastError());
     VArgs a{};
-    a.sym = c->d_sym;  // never d_sym2: the row tables' packs (or symbol ids)
-    a.wave_symoff = c->d_wsym;
-    a.slot_len = c->d_slen;
-    a.slot_seq = c->d_sseq;
+    fill_slot_args(c, a);
     a.slot_out = v.d_slot_out;
     a.psi_off = v.d_psi_off;
     a.tab = v.d_tab;
     a.psi = path ? v.d_psi : nullptr;
     a.logp = v.d_logp;
     a.path = path ? v.d_path : nullptr;
-    a.nslots = P.nslots;
-    a.U = c->U;
     a.N = c->N;
-    a.K = c->K;
-    const long long div = viterbi_pack_div(c->lds_tables(), c->G, 0);  // rows of G entries, no pad column
-    a.div = (int)div;
-    a.shift = viterbi_pack_shift(div);
     const bool lds = viterbi_table_in_lds(c->K, P.GV);
     const bool lr = c->topo == HMMBW_TOPOLOGY_LEFT_TO_RIGHT && P.GV <= 16;
     const VitFn fn = vit_kernel(P.GV, lr, path, lds);

@@ -23,8 +23,7 @@
 // predecessor and the entry-arc bit) and 1 byte per lane (the entry source v), coalesced rows per step and
 // wave; the backtrace runs in the same kernel and loads eight steps' rows at a time (their addresses do not
 // depend on the path), so the dependent step is a cross-lane pick from lane w, never a memory access.
-#include "host.hpp"
-#include "lane_ops.hpp"
+#include "word_units.hpp"
 
 namespace hmmbw {
 
@@ -92,22 +91,6 @@ __device__ __forceinline__ void gmax_idx(double &v, int &i) {
     if constexpr (G >= 16) take(dpp<0x140>(v), dpp_i32<0x140>(i));  // row_mirror
     if constexpr (G >= 32) take(__shfl_xor(v, 16), __shfl_xor(i, 16));
     if constexpr (G >= 64) take(__shfl_xor(v, 32), __shfl_xor(i, 32));
-}
-
-// a lane's N values of one table row (NP doubles, 16-B aligned when NP >= 2)
-template <int N>
-__device__ __forceinline__ void load_row(const double *p, double (&r)[N]) {
-    if constexpr (N == 1) {
-        r[0] = p[0];
-    } else {
-        const double2 *p2 = reinterpret_cast<const double2 *>(p);
-#pragma unroll
-        for (int h = 0; h < (N + 1) / 2; ++h) {
-            const double2 x = p2[h];
-            r[2 * h] = x.x;
-            if (2 * h + 1 < N) r[2 * h + 1] = x.y;
-        }
-    }
 }
 
 template <int GW, int N, bool LR, bool GRAM, bool PATH>
@@ -315,37 +298,16 @@ __global__ void __launch_bounds__(kVitBlock) k_wordnet(WArgs a) {
 
 using WnFn = void (*)(WArgs);
 
-template <int GW, int N>
-static WnFn wn_kernel3(bool lr, bool gram, bool path) {
-    if (lr) {
-        if (gram) return path ? k_wordnet<GW, N, true, true, true> : k_wordnet<GW, N, true, true, false>;
-        return path ? k_wordnet<GW, N, true, false, true> : k_wordnet<GW, N, true, false, false>;
-    }
-    if (gram) return path ? k_wordnet<GW, N, false, true, true> : k_wordnet<GW, N, false, true, false>;
-    return path ? k_wordnet<GW, N, false, false, true> : k_wordnet<GW, N, false, false, false>;
-}
-
-template <int GW>
-static WnFn wn_kernel2(int N, bool lr, bool gram, bool path) {
-    switch (N) {
-        case 1: return wn_kernel3<GW, 1>(lr, gram, path);
-        case 2: return wn_kernel3<GW, 2>(lr, gram, path);
-        case 3: return wn_kernel3<GW, 3>(lr, gram, path);
-        case 4: return wn_kernel3<GW, 4>(lr, gram, path);
-        case 5: return wn_kernel3<GW, 5>(lr, gram, path);
-        case 6: return wn_kernel3<GW, 6>(lr, gram, path);
-        case 7: return wn_kernel3<GW, 7>(lr, gram, path);
-        default: return wn_kernel3<GW, 8>(lr, gram, path);
-    }
-}
-
 static WnFn wn_kernel(int GW, int N, bool lr, bool gram, bool path) {
-    switch (GW) {
-        case 8: return wn_kernel2<8>(N, lr, gram, path);
-        case 16: return wn_kernel2<16>(N, lr, gram, path);
-        case 32: return wn_kernel2<32>(N, lr, gram, path);
-        default: return wn_kernel2<64>(N, lr, gram, path);
-    }
+    return pick_gw_n(GW, N, [=](auto gw, auto n) -> WnFn {
+        constexpr int G = decltype(gw)::value, S = decltype(n)::value;
+        if (lr) {
+            if (gram) return path ? k_wordnet<G, S, true, true, true> : k_wordnet<G, S, true, true, false>;
+            return path ? k_wordnet<G, S, true, false, true> : k_wordnet<G, S, true, false, false>;
+        }
+        if (gram) return path ? k_wordnet<G, S, false, true, true> : k_wordnet<G, S, false, true, false>;
+        return path ? k_wordnet<G, S, false, false, true> : k_wordnet<G, S, false, false, false>;
+    });
 }
 
 void wordnet_free(hmmbw_ctx *c) {
@@ -354,45 +316,19 @@ void wordnet_free(hmmbw_ctx *c) {
     n = hmmbw_ctx::Wordnet{};
 }
 
-// the decoder's buffers for the loaded observations and this bank shape: the back-pointer row offsets of the
-// group width, the staging and table buffers, and with paths the path, the start flags and the back-pointers
+// the decoder's buffers for the loaded observations and this bank shape: what word_decode_buffers keeps, and
+// with paths the path, the start flags and the back-pointers
 static int wordnet_buffers(hmmbw_ctx *c, int GW, size_t n_in, size_t n_tab, bool path) {
-    if (int rc = viterbi_plan_ready(c)) return rc;  // slot_out and the device logp
     hmmbw_ctx::Wordnet &n = c->wn;
-    if (n.GW != GW) {
-        sync_ctx(c);
-        dfree(n.d_psi_off);
-        dfree(n.d_bp);
-        n.GW = 0;
-        ViterbiPlan P = plan_viterbi_group(c->h_slen, c->h_sseq, c->R, GW);
-        if (int rc = dalloc(&n.d_psi_off, P.psi_off.size())) return rc;
-        if (!P.psi_off.empty())
-            HIP_TRY(hipMemcpy(n.d_psi_off, P.psi_off.data(), sizeof(long long) * P.psi_off.size(), hipMemcpyHostToDevice));
-        n.rows = P.psi_rows;
-        n.nvw = P.nvw;
-        n.GW = GW;
-    }
-    if (n.n_in < n_in) {
-        sync_ctx(c);
-        dfree(n.d_in);
-        n.n_in = 0;
-        if (int rc = dalloc(&n.d_in, n_in)) return rc;
-        n.n_in = n_in;
-    }
-    if (n.n_tab < n_tab) {
-        sync_ctx(c);
-        dfree(n.d_tab);
-        n.n_tab = 0;
-        if (int rc = dalloc(&n.d_tab, n_tab)) return rc;
-        n.n_tab = n_tab;
-    }
+    if (int rc = word_decode_buffers(c, n, GW, n_in, n_tab)) return rc;
     if (path) {
         const long long total = c->vit.plan.total;
         int rc = HMMBW_OK;
         if (!n.d_path) rc = dalloc(&n.d_path, (size_t)total);
         if (!rc && !n.d_start) rc = dalloc(&n.d_start, (size_t)total);
         if (!rc && !n.d_bp) rc = dalloc(&n.d_bp, (size_t)n.rows * kWnRowBytes);
-        if (rc) {
+        if (rc) {  // none of the three is kept: the next call with paths allocates them again
+            sync_ctx(c);
             dfree(n.d_path);
             dfree(n.d_start);
             dfree(n.d_bp);
@@ -411,26 +347,17 @@ extern "C" int hmmbw_wordnet_decode(hmmbw_ctx *c, int n_words, const double *pi,
     if (!c) return fail(HMMBW_E_INVALID, "null context");
     if (!c->has_obs) return fail(HMMBW_E_STATE, "observations not set");
     if (int rc = set_device(c)) return rc;
-    if (n_words < 1) return fail(HMMBW_E_INVALID, "n_words " + std::to_string(n_words) + " < 1");
     if (!pi || !A || !B || !logp_out) return fail(HMMBW_E_INVALID, "null argument");
     if (start_out && !path_out) return fail(HMMBW_E_INVALID, "start_out needs path_out");
     if (flags & ~(HMMBW_WORDNET_END_FINAL | HMMBW_WORDNET_DENSE)) return fail(HMMBW_E_INVALID, "unknown flag");
-    if (n_words > kWnMaxWords)
-        return fail(HMMBW_E_UNSUPPORTED, "n_words " + std::to_string(n_words) + " > " + std::to_string(kWnMaxWords));
-    if (c->N > kWnMaxStates)
-        return fail(HMMBW_E_UNSUPPORTED, "word models of N " + std::to_string(c->N) + " > " + std::to_string(kWnMaxStates) + " states");
+    if (int rc = check_word_bank(c, n_words, pi, A, B, kWnMaxWords, kWnMaxStates, "a negative or NaN bank parameter"))
+        return rc;
     const int W = n_words, N = c->N, K = c->K;
     if ((word_init && !wordnet_weights_ok(word_init, W)) || (word_trans && !wordnet_weights_ok(word_trans, (long long)W * W)))
         return fail(HMMBW_E_INVALID, "a negative or NaN word weight");
-    if (!wordnet_weights_ok(pi, (long long)W * N) || !wordnet_weights_ok(A, (long long)W * N * N) ||
-        !wordnet_weights_ok(B, (long long)W * N * K))
-        return fail(HMMBW_E_INVALID, "a negative or NaN bank parameter");
     if (int rc = check_closed(c)) return rc;
     long long total = 0;
-    for (int T : c->h_slen) total += T;
-    if (path_len != total)
-        return fail(HMMBW_E_INVALID, "path_len " + std::to_string(path_len) + " is not the number of loaded symbols (" +
-                                         std::to_string(total) + ")");
+    if (int rc = check_path_len(c, path_len, &total)) return rc;
     if (c->R == 0) return HMMBW_OK;
 
     const bool path = path_out != nullptr, gram = word_trans != nullptr;
@@ -441,25 +368,14 @@ extern "C" int hmmbw_wordnet_decode(hmmbw_ctx *c, int n_words, const double *pi,
     if (int rc = wordnet_buffers(c, GW, (size_t)n_in, (size_t)o.total, path)) return rc;
     hmmbw_ctx::Wordnet &n = c->wn;
 
-    // the bank, staged as one block: pi | A | B | init | G (ones where the caller gave none)
-    std::vector<double> h((size_t)n_in, 1.0);
-    double *hp = h.data();
-    hp = std::copy(pi, pi + (long long)W * N, hp);
-    hp = std::copy(A, A + (long long)W * N * N, hp);
-    hp = std::copy(B, B + (long long)W * N * K, hp);
-    if (word_init) std::copy(word_init, word_init + W, hp);
-    hp += W;
-    if (word_trans) std::copy(word_trans, word_trans + (long long)W * W, hp);
-    HIP_TRY(hipMemcpy(n.d_in, h.data(), sizeof(double) * (size_t)n_in, hipMemcpyHostToDevice));
+    std::vector<double> h;
+    if (int rc = stage_bank(n.d_in, h, n_in, pi, A, B, W, N, K, word_init, word_trans)) return rc;
     hipLaunchKernelGGL(k_wordnet_prep, dim3((unsigned)std::min<long long>((o.total + 255) / 256, 1024)), dim3(256), 0,
                        c->stream, n.d_in, W, N, K, GW, o, n.d_tab);
     HIP_TRY(hipGetLastError());
 
     WArgs a{};
-    a.sym = c->d_sym;  // never d_sym2: the row tables' packs (or symbol ids)
-    a.wave_symoff = c->d_wsym;
-    a.slot_len = c->d_slen;
-    a.slot_seq = c->d_sseq;
+    fill_slot_args(c, a);
     a.slot_out = c->vit.d_slot_out;
     a.psi_off = n.d_psi_off;
     a.tab = n.d_tab;
@@ -467,17 +383,11 @@ extern "C" int hmmbw_wordnet_decode(hmmbw_ctx *c, int n_words, const double *pi,
     a.logp = c->vit.d_logp;
     a.path = path ? n.d_path : nullptr;
     a.start = path ? n.d_start : nullptr;
-    a.nslots = c->vit.plan.nslots;
     a.o_init = o.init;
     a.o_A = o.A;
     a.o_G = o.G;
     a.o_B = o.B;
-    a.U = c->U;
     a.W = W;
-    a.K = K;
-    const long long div = viterbi_pack_div(c->lds_tables(), c->G, 0);  // rows of G entries, no pad column
-    a.div = (int)div;
-    a.shift = viterbi_pack_shift(div);
     a.lds = wordnet_emis_in_lds(K, GW, N) ? 1 : 0;
     a.end_final = (flags & HMMBW_WORDNET_END_FINAL) ? 1 : 0;
     const WnFn fn = wn_kernel(GW, N, lr, gram, path);

@@ -577,6 +577,33 @@ class BaumWelchEngine:
             split = np.split(flat[:total], self._offsets[1:-1]) if self.n_seq else []
         return g, split, logp[: self.n_seq]
 
+    def _word_bank(self, pi, A, B, copy: bool = False):
+        """(W, pi, A, B) of a bank of W word models of the engine's shape as contiguous float64 arrays; copy: never
+        the caller's own arrays (the native call writes into them)."""
+        conv = (lambda x: np.array(x, dtype=np.float64, order="C")) if copy else \
+            (lambda x: np.ascontiguousarray(x, dtype=np.float64))
+        pi = conv(pi)
+        if pi.ndim != 2 or pi.shape[1] != self.N:
+            raise ValueError(f"pi must be [W, {self.N}], not {pi.shape}")
+        W = pi.shape[0]
+        A, B = conv(A), conv(B)
+        if A.shape != (W, self.N, self.N) or B.shape != (W, self.N, self.M):
+            raise ValueError(f"A must be [{W}, {self.N}, {self.N}] and B [{W}, {self.N}, {self.M}], "
+                             f"not {A.shape} and {B.shape}")
+        return W, pi, A, B
+
+    def _transcripts_csr(self, transcripts):
+        """(off, ids, n_pos): one transcript per loaded sequence as CSR, int64 offsets and int32 word ids."""
+        if len(transcripts) != self.n_seq:
+            raise ValueError(f"{len(transcripts)} transcripts for {self.n_seq} loaded sequences")
+        off = np.zeros(len(transcripts) + 1, dtype=np.int64)
+        np.cumsum([len(t) for t in transcripts], out=off[1:])
+        n_pos = int(off[-1])
+        ids = np.zeros(max(n_pos, 1), dtype=np.int32)
+        if n_pos:
+            ids[:n_pos] = np.concatenate([np.asarray(t, dtype=np.int64).reshape(-1) for t in transcripts])
+        return off, ids, n_pos
+
     def wordnet_decode(self, pi, A, B, word_init=None, word_trans=None, end_final: bool = False, dense: bool = False,
                        paths: bool = True):
         """Connected-word decoding of every loaded sequence through a loop of W word models of the engine's shape
@@ -586,15 +613,7 @@ class BaumWelchEngine:
         of every word instance; both None with paths=False (scores only).  end_final: the path ends in a last
         state; dense: the dense within-word scan even for a left-to-right bank.  Needs observations only: the
         engine's own parameters and training state are neither read nor changed."""
-        pi = np.ascontiguousarray(pi, dtype=np.float64)
-        if pi.ndim != 2 or pi.shape[1] != self.N:
-            raise ValueError(f"pi must be [W, {self.N}], not {pi.shape}")
-        W = pi.shape[0]
-        A = np.ascontiguousarray(A, dtype=np.float64)
-        B = np.ascontiguousarray(B, dtype=np.float64)
-        if A.shape != (W, self.N, self.N) or B.shape != (W, self.N, self.M):
-            raise ValueError(f"A must be [{W}, {self.N}, {self.N}] and B [{W}, {self.N}, {self.M}], "
-                             f"not {A.shape} and {B.shape}")
+        W, pi, A, B = self._word_bank(pi, A, B)
         init = None if word_init is None else np.ascontiguousarray(word_init, dtype=np.float64)
         trans = None if word_trans is None else np.ascontiguousarray(word_trans, dtype=np.float64)
         if (init is not None and init.shape != (W,)) or (trans is not None and trans.shape != (W, W)):
@@ -625,22 +644,8 @@ class BaumWelchEngine:
         word; dense: the dense within-word products even for a left-to-right bank; normalise=False returns the
         working parameters, from which a second call continues exactly.  Needs observations only: the engine's own
         parameters and training state are neither read nor changed."""
-        pi = np.array(pi, dtype=np.float64, order="C")
-        if pi.ndim != 2 or pi.shape[1] != self.N:
-            raise ValueError(f"pi must be [W, {self.N}], not {pi.shape}")
-        W = pi.shape[0]
-        A = np.array(A, dtype=np.float64, order="C")
-        B = np.array(B, dtype=np.float64, order="C")
-        if A.shape != (W, self.N, self.N) or B.shape != (W, self.N, self.M):
-            raise ValueError(f"A must be [{W}, {self.N}, {self.N}] and B [{W}, {self.N}, {self.M}], "
-                             f"not {A.shape} and {B.shape}")
-        if len(transcripts) != self.n_seq:
-            raise ValueError(f"{len(transcripts)} transcripts for {self.n_seq} loaded sequences")
-        off = np.zeros(len(transcripts) + 1, dtype=np.int64)
-        np.cumsum([len(t) for t in transcripts], out=off[1:])
-        ids = np.zeros(max(int(off[-1]), 1), dtype=np.int32)
-        if off[-1]:
-            ids[: off[-1]] = np.concatenate([np.asarray(t, dtype=np.int64).reshape(-1) for t in transcripts])
+        W, pi, A, B = self._word_bank(pi, A, B, copy=True)
+        off, ids, _ = self._transcripts_csr(transcripts)
         max_iterations = int(max_iterations)
         recs = (IterRecord * max(max_iterations, 1))()
         n = ctypes.c_int64()
@@ -662,23 +667,8 @@ class BaumWelchEngine:
         None with paths=False (scores only).  logp: the best path's log-probability.  end_final: the path ends in
         the last state of the last word; dense: the dense within-word scan even for a left-to-right bank.  Needs
         observations only: the engine's own parameters and training state are neither read nor changed."""
-        pi = np.ascontiguousarray(pi, dtype=np.float64)
-        if pi.ndim != 2 or pi.shape[1] != self.N:
-            raise ValueError(f"pi must be [W, {self.N}], not {pi.shape}")
-        W = pi.shape[0]
-        A = np.ascontiguousarray(A, dtype=np.float64)
-        B = np.ascontiguousarray(B, dtype=np.float64)
-        if A.shape != (W, self.N, self.N) or B.shape != (W, self.N, self.M):
-            raise ValueError(f"A must be [{W}, {self.N}, {self.N}] and B [{W}, {self.N}, {self.M}], "
-                             f"not {A.shape} and {B.shape}")
-        if len(transcripts) != self.n_seq:
-            raise ValueError(f"{len(transcripts)} transcripts for {self.n_seq} loaded sequences")
-        off = np.zeros(len(transcripts) + 1, dtype=np.int64)
-        np.cumsum([len(t) for t in transcripts], out=off[1:])
-        n_pos = int(off[-1])
-        ids = np.zeros(max(n_pos, 1), dtype=np.int32)
-        if n_pos:
-            ids[:n_pos] = np.concatenate([np.asarray(t, dtype=np.int64).reshape(-1) for t in transcripts])
+        W, pi, A, B = self._word_bank(pi, A, B)
+        off, ids, n_pos = self._transcripts_csr(transcripts)
         flags = (ALIGN_END_FINAL if end_final else 0) | (ALIGN_DENSE if dense else 0)
         logp = np.zeros(max(self.n_seq, 1))
         total = getattr(self, "n_symbols_total", 0)

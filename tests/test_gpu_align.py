@@ -49,14 +49,15 @@ def has_repeat(transcripts):
     return any(a == b for ws in transcripts for a, b in zip(ws, ws[1:]))
 
 
-# every group width, each also just above its power of two; N from 1, 2, 3, 5, 8; both scans.  The last entry is the
+# every group width, each also just above its power of two; every N from 1 to 8; both scans.  The last entry is the
 # seed: one for which, from the checker alone, at least 95 % of the finite sequences clear the margin (two instances
 # of the same word in a row leave the frame of the hand-over open whenever the path sits in the word's last state
 # on both sides of it, so not every draw does)
 WIDTHS = [(1, 3, 3, 8, "left_to_right", 9000), (3, 5, 2, 16, "dense", 9011), (8, 10, 5, 32, "left_to_right", 9001),
           (8, 3, 8, 16, "dense", 9005), (9, 4, 8, 16, "left_to_right", 9001), (16, 8, 1, 8, "dense", 9000),
           (17, 17, 3, 16, "left_to_right", 9000), (33, 6, 5, 32, "dense", 9004), (64, 9, 8, 64, "left_to_right", 9000),
-          (64, 5, 2, 8, "dense", 9000)]
+          (64, 5, 2, 8, "dense", 9000), (3, 4, 6, 16, "dense", 9003), (9, 5, 7, 16, "left_to_right", 9003),
+          (2, 3, 4, 8, "left_to_right", 9002)]
 
 
 def waves_of(obs, spw):

@@ -56,7 +56,8 @@ def compare(got, ref):
 
 # every dense / left-to-right kernel family; (64, 8, 256): the 1 MB emission table that stays in global memory
 BANKS = [(1, 4, 8, "dense"), (3, 3, 8, "left_to_right"), (5, 4, 16, "dense"), (8, 8, 16, "left_to_right"),
-         (10, 5, 32, "left_to_right"), (17, 8, 64, "dense"), (64, 8, 256, "left_to_right")]
+         (10, 5, 32, "left_to_right"), (17, 8, 64, "dense"), (64, 8, 256, "left_to_right"),
+         (3, 6, 16, "left_to_right"), (9, 7, 16, "dense")]
 LONGEST = [1, 2, 8, 9, 16, 17, 33, 64]  # every group width, each also just above its power of two
 _cases = {}
 

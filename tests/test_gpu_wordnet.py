@@ -51,7 +51,7 @@ def run_case(W, N, K, topology, tmin, seed, with_g=True, end_final=False, **kw):
 # every group width, each also just above its power of two; (64, 8, 256): the 1 MB table that stays in global memory
 BANKS = [(1, 4, 8, "dense"), (3, 3, 8, "left_to_right"), (5, 4, 16, "dense"), (8, 8, 16, "left_to_right"),
          (9, 2, 16, "dense"), (10, 5, 32, "left_to_right"), (17, 8, 64, "dense"), (33, 1, 8, "dense"),
-         (64, 8, 256, "left_to_right")]
+         (64, 8, 256, "left_to_right"), (3, 6, 16, "left_to_right"), (9, 7, 16, "dense")]
 
 
 @pytest.mark.parametrize("with_g", [True, False])   # False: word_trans = None, the reduction path

@@ -25,7 +25,7 @@ SHAPES = [("cfg3_lr", 10_000, 200, 8, 256, "left_to_right"), ("cfg3_dense", 10_0
 def spread(us):
     us = np.sort(np.asarray(us))
     return {"median_us": float(np.median(us)), "min_us": float(us[0]), "p10_us": float(np.percentile(us, 10)),
-            "p90_us": float(np.percentile(us, 90)), "n": int(us.size)}
+            "p90_us": float(np.percentile(us, 90)), "max_us": float(us[-1]), "n": int(us.size)}
 
 
 def timed(torch, stream, fn, warmup, reps):
