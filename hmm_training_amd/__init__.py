@@ -10,13 +10,13 @@ __all__ = ["HMMTrained", "DataStorageHMM", "hmm_training", "training_with_save",
            "BaumWelchEngine",
            "lbg_train",
            "createCodeVector", "save_centroids", "train_connected", "frame_table", "mfcc_frames", "mfcc_recordings",
-           "encode_recordings"]
+           "encode_recordings", "with_optional"]
 
 
 def __getattr__(name):
     # the engine-backed entry points load libhmmbw.so (and torch) lazily
     if name in ("hmm_training", "training_with_save", "get_observations", "safe_log", "safe_exp", "log_sum_exp",
-                "train_connected"):
+                "train_connected", "with_optional"):
         from . import hmm_training as _ht
         return getattr(_ht, name)
     if name in ("calculate_log_likelihood", "score_matrix", "test_hmm", "viterbi_decode", "posterior_decode",

@@ -41,7 +41,7 @@ EXPORTED = (
     "hmmbw_cache_trim", "hmmbw_timing_split", "hmmbw_peer_region", "hmmbw_peer_ipc_handle", "hmmbw_peer_open",
     "hmmbw_peer_attach", "hmmbw_allreduce_kind", "hmmbw_status_live_wait", "hmmbw_get_option", "hmmbw_viterbi",
     "hmmbw_posterior", "hmmbw_lbg_train", "hmmbw_wordnet_decode", "hmmbw_embedded_train",
-    "hmmbw_mfcc", "hmmbw_mfcc_tables", "hmmbw_align",
+    "hmmbw_mfcc", "hmmbw_mfcc_tables", "hmmbw_align", "hmmbw_align_optional", "hmmbw_embedded_train_optional",
 )
 ABI_VERSION = 5
 OPT_SAFE_SCALING = 1
@@ -143,6 +143,15 @@ def _declare(lib):
         "hmmbw_align": (ctypes.c_int, [c_ctx, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
                                        ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64, ctypes.c_int, ctypes.c_void_p,
                                        ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p, ctypes.c_int64]),
+        "hmmbw_align_optional": (ctypes.c_int, [c_ctx, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
+                                                ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64,
+                                                ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64,
+                                                ctypes.c_void_p, ctypes.c_int64]),
+        "hmmbw_embedded_train_optional": (ctypes.c_int, [c_ctx, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p,
+                                                         ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
+                                                         ctypes.c_void_p, ctypes.c_int64, ctypes.c_int, ctypes.c_double,
+                                                         ctypes.c_int64, ctypes.c_int, ctypes.c_void_p, ctypes.c_int64,
+                                                         P(ctypes.c_int64), ctypes.c_void_p]),
         "hmmbw_timing": (ctypes.c_int, [c_ctx, ctypes.c_int, P(ctypes.c_double), P(ctypes.c_int64)]),
         "hmmbw_timing_split": (ctypes.c_int, [c_ctx, P(ctypes.c_double), P(ctypes.c_int64)]),
         "hmmbw_peer_region": (ctypes.c_int, [c_ctx, P(ctypes.c_void_p), P(ctypes.c_int64)]),

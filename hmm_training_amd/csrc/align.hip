@@ -22,6 +22,8 @@
 // predecessor and the entry-arc bit), one coalesced 256-byte row per step and wave; the backtrace runs in the same
 // kernel and loads eight steps' rows at a time, so the dependent step is a cross-lane pick from lane l, never a
 // memory access.  Lanes past the transcript's end and padding slots hold -inf throughout and write nothing.
+// hmmbw_align_optional runs the same kernel with OPT: a second entry source two lanes away past an optional
+// position, and one more back-pointer bit per lane and step in a lane mask of its own (align_plan.hpp).
 #include "word_units.hpp"
 #include "align_plan.hpp"
 
@@ -46,6 +48,8 @@ struct AlArgs {
     int div;
     int lds;                     // the emission table is copied to LDS
     int end_final;               // only (L - 1, N - 1) competes for the end
+    const uint8_t *optional;     // OPT: a byte per transcript position, word_ids' order
+    unsigned long long *skip;    // OPT, with paths: [row] the lanes whose entry source is two positions back
 };
 
 // in: pi [W][N] | A [W][N][N] | B [W][N][K]
@@ -57,7 +61,11 @@ __global__ void __launch_bounds__(256) k_align_prep(const double *__restrict__ i
         tab[e] = log(embed_bank_value(pi, A, B, W, N, NP, K, o, e));  // log 0 = -inf in the padding
 }
 
-template <int GW, int N, bool LR, bool PATH>
+// OPT (hmmbw_align_optional with flags): a position with opt = 1 may be passed over.  Position l is then also
+// entered from (l - 2, N - 1) when l - 1 is optional, position 1 also starts a path when position 0 is optional,
+// and a path also ends in L - 2 when L - 1 is optional; on a tie the path that skips less wins.  OPT = false is
+// the kernel as it was.
+template <int GW, int N, bool LR, bool PATH, bool OPT>
 __global__ void __launch_bounds__(kVitBlock) k_align(AlArgs a) {
     extern __shared__ __attribute__((aligned(16))) double sB[];  // a.lds: log B [K][W][NP]
     constexpr int NP = embed_np(N);
@@ -91,6 +99,14 @@ __global__ void __launch_bounds__(kVitBlock) k_align(AlArgs a) {
     const int wid = live ? a.word_ids[woff + l] : 0;
     const size_t kstride = (size_t)a.W * NP, wrow = (size_t)wid * NP;
     const double *lbt = (a.lds ? sB : tabB) + wrow;
+    [[maybe_unused]] bool over = false, start = false, tail_opt = false;  // OPT: l - 1 may be passed over; a path starts here
+    if constexpr (OPT) {
+        over = live && l >= 2 && a.optional[woff + l - 1] != 0;
+        start = l == 0 || (live && l == 1 && a.optional[woff] != 0);
+        tail_opt = Lw >= 2 && a.optional[woff + Lw - 1] != 0;
+    }
+    [[maybe_unused]] unsigned long long *skip = nullptr;
+    if constexpr (OPT && PATH) skip = a.skip + a.psi_off[vw];  // row t: skip[t]
 
     // chunk c of the slot: 8 steps in one 16-B load, U loads further on per chunk (pack_pos)
     const uint4 *pk = reinterpret_cast<const uint4 *>(a.sym) +
@@ -152,9 +168,17 @@ __global__ void __launch_bounds__(kVitBlock) k_align(AlArgs a) {
             unsigned nib = 0;
             if (t == 0) {
 #pragma unroll
-                for (int j = 0; j < N; ++j) nd[j] = l == 0 ? lpi[j] + lb[j] : -INFINITY;
+                for (int j = 0; j < N; ++j) nd[j] = (OPT ? start : l == 0) ? lpi[j] + lb[j] : -INFINITY;
             } else {
-                const double left = from_left<GW>(d[N - 1], l, -INFINITY);
+                double left = from_left<GW>(d[N - 1], l, -INFINITY);
+                if constexpr (OPT) {  // the source two positions back wins only if it is strictly better
+                    const double left2 = from_left2<GW>(d[N - 1], over, -INFINITY);
+                    if constexpr (PATH) {  // off the step's dependent chain
+                        const unsigned long long m = __ballot(left2 > left);
+                        if (lane == 0 && t < Tw) skip[t] = m;
+                    }
+                    left = fmax(left, left2);
+                }
 #pragma unroll
                 for (int j = 0; j < N; ++j) {
                     double best;
@@ -201,7 +225,11 @@ __global__ void __launch_bounds__(kVitBlock) k_align(AlArgs a) {
             v = d[j] > v ? d[j] : v;
         }
     }
-    const int tail = max(Lw - 1, 0);
+    int tail = max(Lw - 1, 0);
+    if constexpr (OPT) {  // an optional last position: L - 2 is an end too, and L - 1 wins ties
+        const double v2 = __shfl(v, max(tail - 1, 0), GW);
+        tail -= tail_opt && v2 > __shfl(v, tail, GW) ? 1 : 0;
+    }
     v = __shfl(v, tail, GW);
     cj = __shfl(cj, tail, GW);
     if (seq >= 0 && l == 0) a.logp[seq] = v;
@@ -209,12 +237,19 @@ __global__ void __launch_bounds__(kVitBlock) k_align(AlArgs a) {
     if constexpr (PATH) {
         const bool valid = v > -INFINITY;
         const long long out = seq >= 0 ? a.slot_out[s] : 0;
-        if (live && !valid) a.bounds[woff + l] = -1;
+        if constexpr (!OPT)
+            if (live && !valid) a.bounds[woff + l] = -1;
         int cl = tail;
+        [[maybe_unused]] int mine = -1;  // OPT: the frame at which this lane's position is entered, -1 if the path passes over it
         for (int t0 = (Tw - 1) / kChunk * kChunk; t0 >= 0; t0 -= kChunk) {
             unsigned p[kChunk];
 #pragma unroll
             for (int k = 0; k < kChunk; ++k) p[k] = t0 + k < T ? bp[(long long)(t0 + k) * kVitWave] : 0u;
+            [[maybe_unused]] unsigned long long sm[OPT ? kChunk : 1];
+            if constexpr (OPT) {  // the group's bits of the eight rows (row 0 is never written: nothing enters at t = 0)
+#pragma unroll
+                for (int k = 0; k < kChunk; ++k) sm[k] = (t0 + k > 0 && t0 + k < T ? skip[t0 + k] : 0ull) >> (lane - l);
+            }
             int ws = -1, wb = -1;  // lane k of the group writes step t0 + k
 #pragma unroll
             for (int k = kChunk - 1; k >= 0; --k) {
@@ -226,41 +261,62 @@ __global__ void __launch_bounds__(kVitBlock) k_align(AlArgs a) {
                         ws = cl * N + cj;
                         wb = (in || t0 + k == 0) ? cl : -1;
                     }
+                    if constexpr (OPT) mine = (in || t0 + k == 0) && cl == l ? t0 + k : mine;
                     cj = in ? N - 1 : (int)(nb & 7u);
-                    cl = in ? cl - 1 : cl;
+                    if constexpr (OPT) cl = in ? cl - 1 - (int)((sm[k] >> cl) & 1ull) : cl;
+                    else cl = in ? cl - 1 : cl;
                 }
             }
             if (seq >= 0 && l < kChunk && t0 + l < T) {
                 a.path[out + t0 + l] = valid ? ws : -1;
-                if (valid && wb >= 0) a.bounds[woff + wb] = t0 + l;
+                if constexpr (!OPT)
+                    if (valid && wb >= 0) a.bounds[woff + wb] = t0 + l;
             }
         }
+        if constexpr (OPT)
+            if (live) a.bounds[woff + l] = valid ? mine : -1;
     }
 }
 
 using AlFn = void (*)(AlArgs);
 
-static AlFn al_kernel(int GW, int N, bool lr, bool path) {
+static AlFn al_kernel(int GW, int N, bool lr, bool path, bool opt) {
     return pick_gw_n(GW, N, [=](auto gw, auto n) -> AlFn {
         constexpr int G = decltype(gw)::value, S = decltype(n)::value;
-        if (lr) return path ? k_align<G, S, true, true> : k_align<G, S, true, false>;
-        return path ? k_align<G, S, false, true> : k_align<G, S, false, false>;
+        if (opt) {
+            if (lr) return path ? k_align<G, S, true, true, true> : k_align<G, S, true, false, true>;
+            return path ? k_align<G, S, false, true, true> : k_align<G, S, false, false, true>;
+        }
+        if (lr) return path ? k_align<G, S, true, true, false> : k_align<G, S, true, false, false>;
+        return path ? k_align<G, S, false, true, false> : k_align<G, S, false, false, false>;
     });
 }
 
 void align_free(hmmbw_ctx *c) {
     hmmbw_ctx::Align &n = c->al;
     dfree(n.d_psi_off); dfree(n.d_in); dfree(n.d_tab); dfree(n.d_word_off); dfree(n.d_word_ids); dfree(n.d_path);
-    dfree(n.d_bounds); dfree(n.d_bp);
+    dfree(n.d_bounds); dfree(n.d_bp); dfree(n.d_opt); dfree(n.d_skip);
     n = hmmbw_ctx::Align{};
 }
 
 // the aligner's buffers for the loaded observations, this bank shape and these transcripts: what
-// word_decode_buffers keeps, the transcripts, and with paths the path, the bounds and the back-pointers
-static int align_buffers(hmmbw_ctx *c, int GW, size_t n_in, size_t n_tab, size_t n_pos, bool path) {
+// word_decode_buffers keeps, the transcripts, and with paths the path, the bounds and the back-pointers; opt: the
+// flags of the optional positions too, and with paths the entry-source masks (planned per width, as d_bp is)
+static int align_buffers(hmmbw_ctx *c, int GW, size_t n_in, size_t n_tab, size_t n_pos, bool path, bool opt) {
     hmmbw_ctx::Align &n = c->al;
+    if (n.GW != GW && n.d_skip) {
+        sync_ctx(c);
+        dfree(n.d_skip);
+    }
     if (int rc = word_decode_buffers(c, n, GW, n_in, n_tab)) return rc;
     if (int rc = grow(c, n.d_word_ids, n.n_ids, n_pos)) return rc;
+    if (opt) {
+        if (int rc = grow(c, n.d_opt, n.n_opt, n_pos)) return rc;
+        if (path && !n.d_skip)
+            if (int rc = dalloc(&n.d_skip, (size_t)n.rows))
+                return fail(rc, "the alignment entry-source masks (" + std::to_string(align_skip_bytes(n.rows)) +
+                                    " bytes) do not fit: " + g_err);
+    }
     if (!n.d_word_off)
         if (int rc = dalloc(&n.d_word_off, (size_t)c->R + 1)) return rc;
     if (path) {
@@ -284,10 +340,13 @@ static int align_buffers(hmmbw_ctx *c, int GW, size_t n_in, size_t n_tab, size_t
 
 }  // namespace hmmbw
 
-extern "C" int hmmbw_align(hmmbw_ctx *c, int n_words, const double *pi, const double *A, const double *B,
-                           const int64_t *word_offsets, const int32_t *word_ids, int64_t n_seq, int flags,
-                           double *logp_out, int32_t *path_out, int64_t path_len, int32_t *bounds_out,
-                           int64_t bounds_len) {
+namespace hmmbw {
+
+// hmmbw_align (optional = nullptr) and hmmbw_align_optional
+static int align_run(hmmbw_ctx *c, int n_words, const double *pi, const double *A, const double *B,
+                     const int64_t *word_offsets, const int32_t *word_ids, const uint8_t *optional, int64_t n_seq,
+                     int flags, double *logp_out, int32_t *path_out, int64_t path_len, int32_t *bounds_out,
+                     int64_t bounds_len) {
     if (!c) return fail(HMMBW_E_INVALID, "null context");
     if (!c->has_obs) return fail(HMMBW_E_STATE, "observations not set");
     if (int rc = set_device(c)) return rc;
@@ -300,6 +359,8 @@ extern "C" int hmmbw_align(hmmbw_ctx *c, int n_words, const double *pi, const do
     const int W = n_words, N = c->N, K = c->K;
     long long longest = 0;
     if (int rc = check_transcripts(word_offsets, word_ids, n_seq, W, kAlMaxWords, &longest, nullptr)) return rc;
+    if (optional)
+        if (int rc = check_optional(word_offsets, word_ids, optional, n_seq, W, nullptr)) return rc;
     if (int rc = check_closed(c)) return rc;
     long long total = 0;
     if (int rc = check_path_len(c, path_len, &total)) return rc;
@@ -309,17 +370,19 @@ extern "C" int hmmbw_align(hmmbw_ctx *c, int n_words, const double *pi, const do
                                          " is not the number of transcript positions (" + std::to_string(n_pos) + ")");
     if (c->R == 0) return HMMBW_OK;
 
-    const bool path = path_out != nullptr;
+    const bool path = path_out != nullptr, opt = optional != nullptr;
     const bool lr = !(flags & HMMBW_ALIGN_DENSE) && wordnet_is_lr(A, W, N);
     const int GW = align_gw((int)longest);
     const EmbedTab o = align_tab(W, N, K);
     const long long n_in = embed_bank_len(W, N, K);
-    if (int rc = align_buffers(c, GW, (size_t)n_in, (size_t)o.total, (size_t)n_pos, path)) return rc;
+    if (int rc = align_buffers(c, GW, (size_t)n_in, (size_t)o.total, (size_t)n_pos, path, opt)) return rc;
     hmmbw_ctx::Align &n = c->al;
 
     std::vector<double> h;
     if (int rc = stage_bank(n.d_in, h, n_in, pi, A, B, W, N, K)) return rc;
     if (int rc = upload_transcripts(n.d_word_off, n.d_word_ids, word_offsets, word_ids, n_seq, n_pos)) return rc;
+    if (opt)
+        if (int rc = upload(n.d_opt, std::vector<unsigned char>(optional, optional + n_pos))) return rc;
     hipLaunchKernelGGL(k_align_prep, dim3((unsigned)std::min<long long>((o.total + 255) / 256, 1024)), dim3(256), 0,
                        c->stream, (const double *)n.d_in, W, N, K, o, n.d_tab);
     HIP_TRY(hipGetLastError());
@@ -340,7 +403,9 @@ extern "C" int hmmbw_align(hmmbw_ctx *c, int n_words, const double *pi, const do
     a.W = W;
     a.lds = embed_emis_in_lds(K, W, N) ? 1 : 0;
     a.end_final = (flags & HMMBW_ALIGN_END_FINAL) ? 1 : 0;
-    const AlFn fn = al_kernel(GW, N, lr, path);
+    a.optional = opt ? n.d_opt : nullptr;
+    a.skip = opt && path ? n.d_skip : nullptr;
+    const AlFn fn = al_kernel(GW, N, lr, path, opt);
     constexpr int wpb = kVitBlock / kVitWave;
     hipLaunchKernelGGL(fn, dim3((unsigned)((n.nvw + wpb - 1) / wpb)), dim3(kVitBlock),
                        a.lds ? embed_emis_bytes(K, W, N) : 0, c->stream, a);
@@ -352,4 +417,22 @@ extern "C" int hmmbw_align(hmmbw_ctx *c, int n_words, const double *pi, const do
         HIP_TRY(hipMemcpyAsync(bounds_out, n.d_bounds, sizeof(int32_t) * (size_t)n_pos, hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(hipStreamSynchronize(c->stream));
     return HMMBW_OK;
+}
+
+}  // namespace hmmbw
+
+extern "C" int hmmbw_align(hmmbw_ctx *c, int n_words, const double *pi, const double *A, const double *B,
+                           const int64_t *word_offsets, const int32_t *word_ids, int64_t n_seq, int flags,
+                           double *logp_out, int32_t *path_out, int64_t path_len, int32_t *bounds_out,
+                           int64_t bounds_len) {
+    return hmmbw::align_run(c, n_words, pi, A, B, word_offsets, word_ids, nullptr, n_seq, flags, logp_out, path_out,
+                            path_len, bounds_out, bounds_len);
+}
+
+extern "C" int hmmbw_align_optional(hmmbw_ctx *c, int n_words, const double *pi, const double *A, const double *B,
+                                    const int64_t *word_offsets, const int32_t *word_ids, const uint8_t *optional,
+                                    int64_t n_seq, int flags, double *logp_out, int32_t *path_out, int64_t path_len,
+                                    int32_t *bounds_out, int64_t bounds_len) {
+    return hmmbw::align_run(c, n_words, pi, A, B, word_offsets, word_ids, optional, n_seq, flags, logp_out, path_out,
+                            path_len, bounds_out, bounds_len);
 }

@@ -28,6 +28,14 @@ static_assert(kAlMaxStates * 4 <= 32, "a nibble per state in one 32-bit word");
 static_assert(kAlMaxStates <= 8, "three bits of predecessor");
 constexpr size_t align_bp_bytes(long long rows) { return (size_t)rows * kAlRowBytes; }
 
+// With optional positions (hmmbw_align_optional) the entry arc has two possible sources, (l - 1, N - 1) and, past
+// an optional position, (l - 2, N - 1).  Both carry the weight log pi_{w_l}[j], so which one wins does not depend
+// on j: one bit per lane and step.  At N = 8 the nibble word is full, so the bits of a (step, wave) row go to a
+// 64-bit lane mask of their own, bit = lane of the wave, 1 = the source two positions back.
+constexpr int kAlSkipRowBytes = 8;
+static_assert(kAlSkipRowBytes * 8 == kVitWave, "a bit per lane of the wave");
+constexpr size_t align_skip_bytes(long long rows) { return (size_t)rows * kAlSkipRowBytes; }
+
 constexpr bool align_flags_ok(int flags) { return (flags & ~kAlFlags) == 0; }
 
 // the output lengths: 0 ok, 1 path_len is not the number of loaded symbols, 2 bounds_len is not the number of

@@ -95,4 +95,36 @@ inline int embed_transcripts_check(const int64_t *off, const int32_t *ids, long 
     return 0;
 }
 
+// Optional transcript positions (hmmbw_embedded_train_optional, hmmbw_align_optional): opt has one byte per
+// position in the CSR order of ids, or is nullptr (no optional position).  A path may pass over a position with
+// opt = 1.  0 ok, 1 a flag other than 0 or 1, 2 two adjacent optional positions, 3 a transcript without a mandatory
+// position.  Call after embed_transcripts_check has accepted the offsets.  mand[w] (W entries, or nullptr) gets the
+// mandatory instances of w, which without flags is embed_transcripts_check's count[w].
+inline int embed_optional_check(const int64_t *off, const int32_t *ids, const uint8_t *opt, long long R, int W,
+                                long long *mand) {
+    if (mand) std::fill(mand, mand + W, 0LL);
+    for (long long r = 0; r < R; ++r) {
+        long long mandatory = 0;
+        for (long long p = off[r]; p < off[r + 1]; ++p) {
+            const int f = opt ? opt[p] : 0;
+            if (f > 1) return 1;
+            if (f && p > off[r] && opt[p - 1]) return 2;
+            if (!f) {
+                ++mandatory;
+                if (mand) ++mand[ids[p]];
+            }
+        }
+        if (mandatory == 0) return 3;
+    }
+    return 0;
+}
+
+// The statistics of the optional path follow EmbedStats' block, which keeps its layout: present [W], the summed
+// entry mass of the optional instances of a word (the M-step adds it to the word's mandatory count for the
+// denominator of pi), and touched [W], nonzero once an M-step has re-estimated the word (a word whose denominator
+// stayed 0 throughout keeps the caller's parameters bit for bit)
+constexpr long long embed_present_off(int W, int N, int K) { return embed_stats(W, N, K).total; }
+constexpr long long embed_touched_off(int W, int N, int K) { return embed_present_off(W, N, K) + W; }
+constexpr long long embed_stats_optional_total(int W, int N, int K) { return embed_touched_off(W, N, K) + W; }
+
 }  // namespace hmmbw

@@ -30,7 +30,7 @@
 // k_embed_mstep (one workgroup per word) re-estimates the tables from the statistics and clears them;
 // k_embed_conv (one workgroup) forms L = LSE_r log P_r, writes the iteration's record and sets done, after which
 // every later launch of the three returns at once.  The host enqueues kEmChunk iterations between two reads of the
-// state.
+// state.  hmmbw_embedded_train_optional runs the same kernels with optional transcript positions (OPT, below).
 #include "word_units.hpp"
 #include "mstep.hpp"  // the element formulas of the M-step
 
@@ -56,6 +56,8 @@ struct EmArgs {
     int div;
     int lds;                     // the emission table is copied to LDS
     int end_final;
+    const uint8_t *optional;     // OPT: a byte per transcript position, word_ids' order
+    long long s_present;         // OPT: EmbedStats' total, where present [W] | touched [W] follow
 };
 
 // in: pi [W][N] | A [W][N][N] | B [W][N][K]
@@ -87,7 +89,12 @@ __device__ __forceinline__ double max_of(const double (&x)[N]) {
     return m;
 }
 
-template <int GW, int N, bool LR>
+// OPT (hmmbw_embedded_train_optional with flags): a position with opt = 1 may be passed over.  alpha_0 is set on
+// position 1 too when position 0 is optional; position l is also entered from (l - 2, N - 1) when l - 1 is optional,
+// so a forward step adds the value two lanes to the left, and beta_t(l, N-1) the entry sum two lanes to the right
+// when l + 1 is optional; beta_{T-1} is also set on L - 2 when L - 1 is optional.  An optional instance adds its
+// entry mass (the probability that it is visited) to present[w].  OPT = false is the kernel as it was.
+template <int GW, int N, bool LR, bool OPT>
 __global__ void __launch_bounds__(kVitBlock) k_embed_estep(EmArgs a) {
     extern __shared__ __attribute__((aligned(16))) double sB[];  // a.lds: B [K][W][NP]
     if (a.state->done) return;  // the whole grid
@@ -121,7 +128,15 @@ __global__ void __launch_bounds__(kVitBlock) k_embed_estep(EmArgs a) {
     }
     const bool live = l < Lw;
     const int wid = live ? a.word_ids[woff + l] : 0;
-    const bool tail = live && l == Lw - 1;  // the last instance
+    const bool last_inst = live && l == Lw - 1;  // the last instance
+    [[maybe_unused]] bool over = false, start = false, self_opt = false, end_opt = false;  // OPT: l - 1 may be passed over; a path starts here
+    if constexpr (OPT) {
+        over = live && l >= 2 && a.optional[woff + l - 1] != 0;
+        start = l == 0 || (live && l == 1 && a.optional[woff] != 0);
+        self_opt = live && a.optional[woff + l] != 0;
+        end_opt = live && l == Lw - 2 && a.optional[woff + Lw - 1] != 0;
+    }
+    const bool tail = OPT ? last_inst || end_opt : last_inst;  // an instance a path may end in
     const size_t kstride = (size_t)a.W * NP, wrow = (size_t)wid * NP;
     const double *bt = (a.lds ? sB : tabB) + wrow;
 
@@ -173,7 +188,8 @@ __global__ void __launch_bounds__(kVitBlock) k_embed_estep(EmArgs a) {
             if (t >= Tw) break;  // the whole wave
             double b[N];
             load_row<N>(bt + (size_t)symbol(q, k) * kstride, b);
-            const double left = from_left<GW>(al[N - 1], l, 0.0);
+            double left = from_left<GW>(al[N - 1], l, 0.0);
+            if constexpr (OPT) left += from_left2<GW>(al[N - 1], over, 0.0);
             double nd[N];
 #pragma unroll
             for (int j = 0; j < N; ++j) {
@@ -187,7 +203,7 @@ __global__ void __launch_bounds__(kVitBlock) k_embed_estep(EmArgs a) {
                     for (int i = 1; i < N; ++i) x = fma(al[i], ca[i * N + j], x);
                 }
                 x = fma(left, pi[j], x);
-                if (t == 0) x = l == 0 ? pi[j] : 0.0;
+                if (t == 0) x = (OPT ? start : l == 0) ? pi[j] : 0.0;
                 nd[j] = x * b[j];
             }
             const int e = group_exp<GW>(max_of<N>(nd));  // kZeroExp: the whole group is zero, and stays zero
@@ -240,8 +256,12 @@ __global__ void __launch_bounds__(kVitBlock) k_embed_estep(EmArgs a) {
                 v[j] = bn[j] * be[j];
                 es = fma(pi[j], v[j], es);
             }
-            const double right = from_right<GW>(es, l, 0.0);
-            const double aleft = from_left<GW>(at[N - 1], l, 0.0);
+            double right = from_right<GW>(es, l, 0.0);
+            double aleft = from_left<GW>(at[N - 1], l, 0.0);
+            if constexpr (OPT) {  // this instance's entry sum also reaches l - 2 when l - 1 is optional
+                right += from_right2<GW>(over ? es : 0.0, l, 0.0);
+                aleft += from_left2<GW>(at[N - 1], over, 0.0);
+            }
             double bp[N];  // beta_t before its rescale
 #pragma unroll
             for (int i = 0; i < N; ++i) {
@@ -267,7 +287,7 @@ __global__ void __launch_bounds__(kVitBlock) k_embed_estep(EmArgs a) {
             for (int j = 0; j < N; ++j) {
                 const double g = at[j] * bp[j] * inv;
                 ga[j] += g;
-                if (t == 0 && l == 0) en[j] += g;
+                if (t == 0 && (OPT ? start : l == 0)) en[j] += g;
                 if (g > 0.0) atomicAdd(bnum + (size_t)o * kstride + j, g);
             }
             const double ainv = last ? 0.0 : inv;  // no arc leaves the last row
@@ -298,6 +318,12 @@ __global__ void __launch_bounds__(kVitBlock) k_embed_estep(EmArgs a) {
     if (live && !dead) {
         double *sen = a.stats + (long long)wid * N, *sga = a.stats + a.s_gall + (long long)wid * N;
         double *sxi = a.stats + a.s_xi + (long long)wid * N * N;
+        if constexpr (OPT) {
+            double mass = 0.0;
+#pragma unroll
+            for (int j = 0; j < N; ++j) mass += en[j];
+            if (self_opt && mass > 0.0) atomicAdd(a.stats + a.s_present + wid, mass);
+        }
 #pragma unroll
         for (int j = 0; j < N; ++j) {
             if (en[j] > 0.0) atomicAdd(sen + j, en[j]);
@@ -315,12 +341,17 @@ __global__ void __launch_bounds__(kVitBlock) k_embed_estep(EmArgs a) {
 }
 
 // One workgroup per word: the M-step of hmm_training.py:415-500 from the word's statistics into the tables the
-// next E-step reads; the statistics are cleared.  A word without an instance keeps its parameters.
+// next E-step reads; the statistics are cleared.  A word without an instance keeps its parameters.  With optional
+// positions (a.optional set) count[w] holds the mandatory instances and the denominator of pi is count[w] +
+// present[w]; a word whose denominator is 0 keeps its parameters, and touched[w] is set for every other word.
 __global__ void __launch_bounds__(256) k_embed_mstep(EmArgs a, int N, const long long *__restrict__ count) {
     __shared__ double sDen[kEmMaxStates], sInv[kEmMaxStates];
     if (a.state->done) return;
     const int w = blockIdx.x, tid = threadIdx.x, NP = embed_np(N);
     const long long cnt = count[w];
+    double *present = a.optional ? a.stats + a.s_present + w : nullptr;
+    const double den_pi = present ? (double)cnt + *present : (double)cnt;
+    const bool upd = den_pi > 0.0;
     double *sen = a.stats + (long long)w * N, *sga = a.stats + a.s_gall + (long long)w * N;
     double *sxi = a.stats + a.s_xi + (long long)w * N * N;
     if (tid < N) {
@@ -330,17 +361,21 @@ __global__ void __launch_bounds__(256) k_embed_mstep(EmArgs a, int N, const long
         sInv[tid] = mstep_inv(sga[tid]);
     }
     __syncthreads();
-    if (cnt > 0) {
-        if (tid < N) a.tab[(long long)w * NP + tid] = mstep_pi(sen[tid], cnt);
+    if (upd) {
+        if (tid < N) a.tab[(long long)w * NP + tid] = present ? mstep_a(sen[tid], den_pi) : mstep_pi(sen[tid], cnt);
         if (tid < N * N) a.tab[a.o_A + (long long)w * N * N + tid] = mstep_a(sxi[tid], sDen[tid / N]);
     }
     __syncthreads();
+    if (present && tid == 0) {
+        *present = 0.0;
+        if (upd) present[a.W] = 1.0;  // touched
+    }
     if (tid < N) sen[tid] = sga[tid] = 0.0;
     if (tid < N * N) sxi[tid] = 0.0;
     for (int idx = tid; idx < a.K * NP; idx += blockDim.x) {
         const int k = idx / NP, j = idx % NP;
         const long long at = ((long long)k * a.W + w) * NP + j;
-        if (j < N && cnt > 0) a.tab[a.o_B + at] = bnum_to_b(a.stats[a.s_bnum + at], sInv[j]);
+        if (j < N && upd) a.tab[a.o_B + at] = bnum_to_b(a.stats[a.s_bnum + at], sInv[j]);
         a.stats[a.s_bnum + at] = 0.0;
     }
 }
@@ -407,10 +442,11 @@ __global__ void __launch_bounds__(256) k_embed_export(const double *__restrict__
 
 using EmFn = void (*)(EmArgs);
 
-static EmFn em_kernel(int GW, int N, bool lr) {
+static EmFn em_kernel(int GW, int N, bool lr, bool opt) {
     return pick_gw_n(GW, N, [=](auto gw, auto n) -> EmFn {
         constexpr int G = decltype(gw)::value, S = decltype(n)::value;
-        return lr ? k_embed_estep<G, S, true> : k_embed_estep<G, S, false>;
+        if (opt) return lr ? k_embed_estep<G, S, true, true> : k_embed_estep<G, S, false, true>;
+        return lr ? k_embed_estep<G, S, true, false> : k_embed_estep<G, S, false, false>;
     });
 }
 
@@ -419,12 +455,13 @@ struct EmWork {
     double *in = nullptr, *tab = nullptr, *stats = nullptr, *work = nullptr, *logp = nullptr;
     long long *work_off = nullptr, *word_off = nullptr, *count = nullptr;
     int *word_ids = nullptr;
+    unsigned char *optional = nullptr;
     EmbedState *state = nullptr;
     hmmbw_ctx *c = nullptr;
     ~EmWork() {
         sync_ctx(c);
         dfree(in); dfree(tab); dfree(stats); dfree(work); dfree(logp);
-        dfree(work_off); dfree(word_off); dfree(count); dfree(word_ids); dfree(state);
+        dfree(work_off); dfree(word_off); dfree(count); dfree(word_ids); dfree(optional); dfree(state);
     }
 };
 
@@ -436,10 +473,13 @@ static int to_device(T **d, const std::vector<T> &h) {
 
 }  // namespace hmmbw
 
-extern "C" int hmmbw_embedded_train(hmmbw_ctx *c, int n_words, double *pi, double *A, double *B,
-                                    const int64_t *word_offsets, const int32_t *word_ids, int64_t n_seq, int flags,
-                                    double epsilon, int64_t max_iterations, int normalise, hmmbw_iter_record *records,
-                                    int64_t records_cap, int64_t *n_records, double *logp_out) {
+namespace hmmbw {
+
+// hmmbw_embedded_train (optional = nullptr) and hmmbw_embedded_train_optional
+static int embedded_run(hmmbw_ctx *c, int n_words, double *pi, double *A, double *B, const int64_t *word_offsets,
+                        const int32_t *word_ids, const uint8_t *optional, int64_t n_seq, int flags, double epsilon,
+                        int64_t max_iterations, int normalise, hmmbw_iter_record *records, int64_t records_cap,
+                        int64_t *n_records, double *logp_out) {
     if (!c) return fail(HMMBW_E_INVALID, "null context");
     if (!c->has_obs) return fail(HMMBW_E_STATE, "observations not set");
     if (int rc = set_device(c)) return rc;
@@ -456,6 +496,9 @@ extern "C" int hmmbw_embedded_train(hmmbw_ctx *c, int n_words, double *pi, doubl
     long long longest = 0;
     std::vector<long long> count((size_t)W, 0);
     if (int rc = check_transcripts(word_offsets, word_ids, n_seq, W, kEmMaxWords, &longest, count.data())) return rc;
+    const bool opt = optional != nullptr;
+    if (opt)  // count: the mandatory instances
+        if (int rc = check_optional(word_offsets, word_ids, optional, n_seq, W, count.data())) return rc;
     if (int rc = check_closed(c)) return rc;
     if (n_records) *n_records = 0;
     if (c->R == 0) return HMMBW_OK;
@@ -465,6 +508,7 @@ extern "C" int hmmbw_embedded_train(hmmbw_ctx *c, int n_words, double *pi, doubl
     const EmbedTab o = embed_tab(W, N, K);
     const EmbedStats so = embed_stats(W, N, K);
     const long long n_bank = embed_bank_len(W, N, K);
+    const long long n_stats = opt ? embed_stats_optional_total(W, N, K) : so.total;
     const ViterbiPlan P = plan_viterbi_group(c->h_slen, c->h_sseq, c->R, GW);
 
     EmWork w;
@@ -474,7 +518,7 @@ extern "C" int hmmbw_embedded_train(hmmbw_ctx *c, int n_words, double *pi, doubl
                             " bytes) does not fit: " + g_err);
     if (int rc = dalloc(&w.in, (size_t)n_bank)) return rc;
     if (int rc = dalloc(&w.tab, (size_t)o.total)) return rc;
-    if (int rc = dalloc(&w.stats, (size_t)so.total)) return rc;
+    if (int rc = dalloc(&w.stats, (size_t)n_stats)) return rc;
     if (int rc = dalloc(&w.logp, (size_t)c->R)) return rc;
     if (int rc = dalloc(&w.state, 1)) return rc;
     if (int rc = to_device(&w.work_off, P.psi_off)) return rc;
@@ -483,11 +527,13 @@ extern "C" int hmmbw_embedded_train(hmmbw_ctx *c, int n_words, double *pi, doubl
     if (int rc = dalloc(&w.word_off, (size_t)n_seq + 1)) return rc;
     if (int rc = dalloc(&w.word_ids, (size_t)n_pos)) return rc;
     if (int rc = upload_transcripts(w.word_off, w.word_ids, word_offsets, word_ids, n_seq, n_pos)) return rc;
+    if (opt)
+        if (int rc = to_device(&w.optional, std::vector<unsigned char>(optional, optional + n_pos))) return rc;
     std::vector<double> h;  // the staged bank, and the trained one on the way back
     if (int rc = stage_bank(w.in, h, n_bank, pi, A, B, W, N, K)) return rc;
-    const long long nprep = std::max(o.total, so.total);
+    const long long nprep = std::max(o.total, n_stats);
     hipLaunchKernelGGL(k_embed_prep, dim3((unsigned)std::min<long long>((nprep + 255) / 256, 1024)), dim3(256), 0,
-                       c->stream, w.in, W, N, K, o, w.tab, w.stats, so.total, w.state, epsilon, (long long)max_iterations);
+                       c->stream, w.in, W, N, K, o, w.tab, w.stats, n_stats, w.state, epsilon, (long long)max_iterations);
     HIP_TRY(hipGetLastError());
 
     EmArgs a{};
@@ -508,7 +554,9 @@ extern "C" int hmmbw_embedded_train(hmmbw_ctx *c, int n_words, double *pi, doubl
     a.W = W;
     a.lds = embed_emis_in_lds(K, W, N) ? 1 : 0;
     a.end_final = (flags & HMMBW_EMBED_END_FINAL) ? 1 : 0;
-    const EmFn fn = em_kernel(GW, N, lr);
+    a.optional = w.optional;
+    a.s_present = embed_present_off(W, N, K);
+    const EmFn fn = em_kernel(GW, N, lr, opt);
     constexpr int wpb = kVitBlock / kVitWave;
     const unsigned grid = (unsigned)((P.nvw + wpb - 1) / wpb);
     const size_t lds = a.lds ? embed_emis_bytes(K, W, N) : 0;
@@ -541,14 +589,39 @@ extern "C" int hmmbw_embedded_train(hmmbw_ctx *c, int n_words, double *pi, doubl
     HIP_TRY(hipMemcpyAsync(h.data(), w.in, sizeof(double) * (size_t)n_bank, hipMemcpyDeviceToHost, c->stream));
     if (logp_out)
         HIP_TRY(hipMemcpyAsync(logp_out, w.logp, sizeof(double) * (size_t)c->R, hipMemcpyDeviceToHost, c->stream));
+    std::vector<double> touched;  // opt: nonzero for the words an M-step re-estimated
+    if (opt) {
+        touched.resize((size_t)W);
+        HIP_TRY(hipMemcpyAsync(touched.data(), w.stats + embed_touched_off(W, N, K), sizeof(double) * (size_t)W,
+                               hipMemcpyDeviceToHost, c->stream));
+    }
     HIP_TRY(hipStreamSynchronize(c->stream));
-    // a word without an instance keeps the caller's values bit for bit
+    // a word without an instance (opt: whose denominator was 0 in every iteration) keeps the caller's values bit for bit
     const double *hpi = h.data(), *hA = hpi + (long long)W * N, *hB = hA + (long long)W * N * N;
     for (long long x = 0; x < W; ++x) {
-        if (count[(size_t)x] == 0) continue;
+        if (opt ? touched[(size_t)x] == 0.0 : count[(size_t)x] == 0) continue;
         std::copy(hpi + x * N, hpi + (x + 1) * N, pi + x * N);
         std::copy(hA + x * N * N, hA + (x + 1) * N * N, A + x * N * N);
         std::copy(hB + x * N * K, hB + (x + 1) * N * K, B + x * N * K);
     }
     return HMMBW_OK;
+}
+
+}  // namespace hmmbw
+
+extern "C" int hmmbw_embedded_train(hmmbw_ctx *c, int n_words, double *pi, double *A, double *B,
+                                    const int64_t *word_offsets, const int32_t *word_ids, int64_t n_seq, int flags,
+                                    double epsilon, int64_t max_iterations, int normalise, hmmbw_iter_record *records,
+                                    int64_t records_cap, int64_t *n_records, double *logp_out) {
+    return hmmbw::embedded_run(c, n_words, pi, A, B, word_offsets, word_ids, nullptr, n_seq, flags, epsilon,
+                               max_iterations, normalise, records, records_cap, n_records, logp_out);
+}
+
+extern "C" int hmmbw_embedded_train_optional(hmmbw_ctx *c, int n_words, double *pi, double *A, double *B,
+                                             const int64_t *word_offsets, const int32_t *word_ids,
+                                             const uint8_t *optional, int64_t n_seq, int flags, double epsilon,
+                                             int64_t max_iterations, int normalise, hmmbw_iter_record *records,
+                                             int64_t records_cap, int64_t *n_records, double *logp_out) {
+    return hmmbw::embedded_run(c, n_words, pi, A, B, word_offsets, word_ids, optional, n_seq, flags, epsilon,
+                               max_iterations, normalise, records, records_cap, n_records, logp_out);
 }

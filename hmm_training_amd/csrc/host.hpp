@@ -205,6 +205,10 @@ struct hmmbw_ctx {
         size_t n_ids = 0, n_bounds = 0;    // lengths in elements
         int32_t *d_bounds = nullptr;       // with paths only: caller CSR order of the transcripts
         unsigned *d_bp = nullptr;          // with paths only: rows x 64 lanes
+        // hmmbw_align_optional with flags only
+        unsigned char *d_opt = nullptr;    // a byte per transcript position, d_word_ids' order
+        size_t n_opt = 0;
+        unsigned long long *d_skip = nullptr;  // with paths: rows lane masks (align_plan.hpp, align_skip_bytes)
     } al;
     // native RCCL communicator (hmmbw_comm_init): the multi-rank hmmbw_iterate all-reduces d_ext
     ncclComm_t comm = nullptr;

@@ -49,6 +49,24 @@ __device__ __forceinline__ double from_right(double x, int l, double edge) {
     else nb = __shfl_down(x, 1, GW);
     return l < GW - 1 ? nb : edge;
 }
+// the value of lane l - 2 / l + 2 of the group (the source past an optional transcript position).  A 16-lane DPP
+// row holds two groups of 8: the two lanes at the group's edge take the edge value, never the other group's.
+// from_left2 takes the lane's own condition in place of l (take implies l >= 2: position l - 1 is optional), so that
+// the edge and the flag cost one select.
+template <int GW>
+__device__ __forceinline__ double from_left2(double x, bool take, double edge) {
+    double nb;
+    if constexpr (GW <= 16) nb = dpp<0x112>(x);  // row_shr:2
+    else nb = __shfl_up(x, 2, GW);
+    return take ? nb : edge;
+}
+template <int GW>
+__device__ __forceinline__ double from_right2(double x, int l, double edge) {
+    double nb;
+    if constexpr (GW <= 16) nb = dpp<0x102>(x);  // row_shl:2
+    else nb = __shfl_down(x, 2, GW);
+    return l < GW - 2 ? nb : edge;
+}
 
 // element e of the EmbedTab tables (embed_plan.hpp, NP = embed_np(N)) from the staged linear bank pi [W][N] |
 // A [W][N][N] | B [W][N][K]; 0 in the padding.  The callers form the three pointers and NP before their loops: taking
@@ -164,6 +182,17 @@ inline int check_transcripts(const int64_t *off, const int32_t *ids, int64_t n_s
     if (*longest > max_words)
         return fail(HMMBW_E_UNSUPPORTED, "a transcript of " + std::to_string(*longest) + " words > " + std::to_string(max_words));
     return HMMBW_OK;
+}
+
+// embed_optional_check's verdict as its message (opt may be nullptr: nothing to check but the count)
+inline int check_optional(const int64_t *off, const int32_t *ids, const uint8_t *opt, int64_t n_seq, int W,
+                          long long *mand) {
+    switch (embed_optional_check(off, ids, opt, n_seq, W, mand)) {
+        case 0: return HMMBW_OK;
+        case 1: return fail(HMMBW_E_INVALID, "an optional flag other than 0 or 1");
+        case 2: return fail(HMMBW_E_INVALID, "two adjacent optional transcript positions");
+        default: return fail(HMMBW_E_INVALID, "a transcript without a mandatory position");
+    }
 }
 
 template <class T>

@@ -604,6 +604,20 @@ class BaumWelchEngine:
             ids[:n_pos] = np.concatenate([np.asarray(t, dtype=np.int64).reshape(-1) for t in transcripts])
         return off, ids, n_pos
 
+    def _optional_flags(self, optional, transcripts, n_pos):
+        """One uint8 per transcript position in CSR order from one boolean sequence per transcript, or None."""
+        if optional is None:
+            return None
+        if len(optional) != len(transcripts):
+            raise ValueError(f"{len(optional)} optional sequences for {len(transcripts)} transcripts")
+        for r, (o, t) in enumerate(zip(optional, transcripts)):
+            if len(o) != len(t):
+                raise ValueError(f"optional[{r}] has {len(o)} entries for a transcript of {len(t)} positions")
+        flags = np.zeros(max(n_pos, 1), dtype=np.uint8)
+        if n_pos:
+            flags[:n_pos] = np.concatenate([np.asarray(o, dtype=bool).reshape(-1) for o in optional])
+        return flags
+
     def wordnet_decode(self, pi, A, B, word_init=None, word_trans=None, end_final: bool = False, dense: bool = False,
                        paths: bool = True):
         """Connected-word decoding of every loaded sequence through a loop of W word models of the engine's shape
@@ -635,49 +649,64 @@ class BaumWelchEngine:
         return np.split(flat[:total], cut), np.split(first[:total], cut), logp[: self.n_seq]
 
     def embedded_train(self, pi, A, B, transcripts, epsilon: float = 1e-6, max_iterations: int = 100,
-                       end_final: bool = False, dense: bool = False, normalise: bool = True):
+                       end_final: bool = False, dense: bool = False, normalise: bool = True, optional=None):
         """Embedded Baum-Welch training of a bank of W word models of the engine's shape from the loaded sequences
         and their transcripts (hmmbw_embedded_train): (pi, A, B, records, logp).  pi [W, N], A [W, N, N],
         B [W, N, M] are the start bank (the arguments are not changed); transcripts[r] lists the word ids spoken in
         sequence r, in order.  records: the (L, diff) of every iteration made; logp: log P_r of the last E-step
         (-inf where no path explains the sequence).  end_final: an utterance ends in the last state of its last
         word; dense: the dense within-word products even for a left-to-right bank; normalise=False returns the
-        working parameters, from which a second call continues exactly.  Needs observations only: the engine's own
-        parameters and training state are neither read nor changed."""
+        working parameters, from which a second call continues exactly.  optional: one boolean sequence per
+        transcript, True where the position may be passed over (hmmbw_embedded_train_optional: no two adjacent
+        optional positions, a mandatory one in every transcript); a word named only at optional positions that the
+        data never visits comes back unchanged.  Needs observations only: the engine's own parameters and training
+        state are neither read nor changed."""
         W, pi, A, B = self._word_bank(pi, A, B, copy=True)
-        off, ids, _ = self._transcripts_csr(transcripts)
+        off, ids, n_pos = self._transcripts_csr(transcripts)
+        opt = self._optional_flags(optional, transcripts, n_pos)
         max_iterations = int(max_iterations)
         recs = (IterRecord * max(max_iterations, 1))()
         n = ctypes.c_int64()
         logp = np.zeros(max(self.n_seq, 1))
         flags = (EMBED_END_FINAL if end_final else 0) | (EMBED_DENSE if dense else 0)
-        check(self._lib.hmmbw_embedded_train(
-            self._ctx, W, pi.ctypes.data, A.ctypes.data, B.ctypes.data, off.ctypes.data, ids.ctypes.data, self.n_seq,
-            flags, float(epsilon), max_iterations, int(normalise), ctypes.cast(recs, ctypes.c_void_p),
-            max(max_iterations, 1), ctypes.byref(n), logp.ctypes.data))
+        tail = (self.n_seq, flags, float(epsilon), max_iterations, int(normalise), ctypes.cast(recs, ctypes.c_void_p),
+                max(max_iterations, 1), ctypes.byref(n), logp.ctypes.data)
+        head = (self._ctx, W, pi.ctypes.data, A.ctypes.data, B.ctypes.data, off.ctypes.data, ids.ctypes.data)
+        if opt is None:
+            check(self._lib.hmmbw_embedded_train(*head, *tail))
+        else:
+            check(self._lib.hmmbw_embedded_train_optional(*head, opt.ctypes.data, *tail))
         records = [(recs[i].log_likelihood, recs[i].diff) for i in range(n.value)]
         return pi, A, B, records, logp[: self.n_seq]
 
-    def align(self, pi, A, B, transcripts, end_final: bool = False, dense: bool = False, paths: bool = True):
+    def align(self, pi, A, B, transcripts, end_final: bool = False, dense: bool = False, paths: bool = True,
+              optional=None):
         """Forced alignment of every loaded sequence to its transcript through a bank of W word models of the
         engine's shape (hmmbw_align): (paths, bounds, logp).  pi [W, N], A [W, N, N], B [W, N, M]; transcripts[r]
         lists the word ids spoken in sequence r, in order.  paths: one int32 array of composite states l N + j per
         sequence, l the transcript position; bounds: one int32 array per sequence, the first frame of every
         position (position l ends where l + 1 starts, the last one at T); both all -1 where logp is -inf, and both
         None with paths=False (scores only).  logp: the best path's log-probability.  end_final: the path ends in
-        the last state of the last word; dense: the dense within-word scan even for a left-to-right bank.  Needs
-        observations only: the engine's own parameters and training state are neither read nor changed."""
+        the last state of the last word; dense: the dense within-word scan even for a left-to-right bank.
+        optional: one boolean sequence per transcript, True where the position may be passed over
+        (hmmbw_align_optional); the bound of a position the path passes over is -1, and l stays the index in the
+        transcript as given.  Needs observations only: the engine's own parameters and training state are neither
+        read nor changed."""
         W, pi, A, B = self._word_bank(pi, A, B)
         off, ids, n_pos = self._transcripts_csr(transcripts)
+        opt = self._optional_flags(optional, transcripts, n_pos)
         flags = (ALIGN_END_FINAL if end_final else 0) | (ALIGN_DENSE if dense else 0)
         logp = np.zeros(max(self.n_seq, 1))
         total = getattr(self, "n_symbols_total", 0)
         flat = np.zeros(max(total, 1), dtype=np.int32) if paths else None
         first = np.zeros(max(n_pos, 1), dtype=np.int32) if paths else None
-        check(self._lib.hmmbw_align(
-            self._ctx, W, pi.ctypes.data, A.ctypes.data, B.ctypes.data, off.ctypes.data, ids.ctypes.data, self.n_seq,
-            flags, logp.ctypes.data, flat.ctypes.data if paths else None, total,
-            first.ctypes.data if paths else None, n_pos))
+        head = (self._ctx, W, pi.ctypes.data, A.ctypes.data, B.ctypes.data, off.ctypes.data, ids.ctypes.data)
+        tail = (self.n_seq, flags, logp.ctypes.data, flat.ctypes.data if paths else None, total,
+                first.ctypes.data if paths else None, n_pos)
+        if opt is None:
+            check(self._lib.hmmbw_align(*head, *tail))
+        else:
+            check(self._lib.hmmbw_align_optional(*head, opt.ctypes.data, *tail))
         if not paths:
             return None, None, logp[: self.n_seq]
         if not self.n_seq:

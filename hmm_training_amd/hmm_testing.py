@@ -13,7 +13,7 @@ import numpy as np
 
 from .engine import BaumWelchEngine, EngineGroup
 from .hmm_classes import HMMTrained
-from .hmm_training import get_observations, transcript_ids
+from .hmm_training import _check_optional, get_observations, transcript_ids
 
 
 def score_matrix(observations: Sequence[np.ndarray], models: Sequence[HMMTrained], device=None) -> np.ndarray:
@@ -121,14 +121,16 @@ def decode_words(observations: Sequence[np.ndarray], models: Sequence[HMMTrained
 
 
 def align_words(observations: Sequence[np.ndarray], transcripts: Sequence[Sequence], models: Sequence[HMMTrained],
-                end_final: bool = True, device=None) -> Tuple[List[List[Tuple[object, int, int]]], np.ndarray]:
+                end_final: bool = True, device=None, optional=None) -> Tuple[List[List[Tuple[object, int, int]]], np.ndarray]:
     """(segments, logp): where each word of a known utterance lies: the best path of every recording through the
     chain of the word models its transcript names, all sequences in one launch (BaumWelchEngine.align).
     transcripts[r] lists the models' .word names spoken in recording r, as train_connected takes them.  segments[r]
     lists (word, start_frame, end_frame_exclusive), one per transcript position, in order; it is [] where no path
     explains the recording (logp -inf; a recording shorter than its transcript is one).  end_final: every
-    recording ends in the last state of its last word, as train_connected and decode_words assume by default.  The
-    models must share one shape."""
+    recording ends in the last state of its last word, as train_connected and decode_words assume by default.
+    optional: one boolean sequence per transcript, True where the position may be passed over (with_optional builds
+    the usual `sil? one sil? two sil?`); a position the path passes over gives no segment, and a segment ends where
+    the next visited position starts.  The models must share one shape."""
     if len(models) == 0:
         raise ValueError("no word models")
     N, M = int(models[0].states), int(np.asarray(models[0].B).shape[1])
@@ -138,6 +140,7 @@ def align_words(observations: Sequence[np.ndarray], transcripts: Sequence[Sequen
     if len(transcripts) != len(observations):
         raise ValueError(f"{len(transcripts)} transcripts for {len(observations)} recordings")
     ids = transcript_ids(transcripts, models)
+    _check_optional(optional, transcripts)
     if len(observations) == 0:
         return [], np.zeros(0)
     pi = np.stack([np.asarray(h.Pi, dtype=np.float64).reshape(N) for h in models])
@@ -145,14 +148,15 @@ def align_words(observations: Sequence[np.ndarray], transcripts: Sequence[Sequen
     B = np.stack([np.asarray(h.B, dtype=np.float64) for h in models])
     with BaumWelchEngine(N, M, device=device) as eng:
         eng.set_observations(list(observations))
-        _, bounds, logp = eng.align(pi, A, B, ids, end_final=end_final)
+        _, bounds, logp = eng.align(pi, A, B, ids, end_final=end_final, optional=optional)
     segments = []
     for r, (b, words) in enumerate(zip(bounds, ids)):
         if logp[r] == -np.inf:
             segments.append([])
             continue
-        ends = np.append(b[1:], len(observations[r]))
-        segments.append([(models[w].word, int(s), int(e)) for w, s, e in zip(words, b, ends)])
+        seen = np.flatnonzero(b >= 0)          # the visited positions
+        ends = np.append(b[seen][1:], len(observations[r]))
+        segments.append([(models[words[l]].word, int(b[l]), int(e)) for l, e in zip(seen, ends)])
     return segments, logp
 
 

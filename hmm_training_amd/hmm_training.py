@@ -348,14 +348,46 @@ def transcript_ids(transcripts: Sequence[Sequence], models: Sequence[HMMTrained]
     return ids
 
 
+def with_optional(transcripts: Sequence[Sequence], word) -> Tuple[List[list], List[List[bool]]]:
+    """(transcripts, optional) with `word` inserted as an optional position before, between and after the given
+    words: ["one", "two"] becomes ["sil", "one", "sil", "two", "sil"] with flags [True, False, True, False, True], the
+    transcript `sil? one sil? two sil?` of a recording whose pauses nobody marked (train_connected, align_words)."""
+    out, flags = [], []
+    for r, words in enumerate(transcripts):
+        words = list(words)
+        if not words:
+            raise ValueError(f"transcript {r} is empty")
+        if word in words:
+            raise ValueError(f"transcript {r} already names {word!r}: two neighbouring positions would be optional "
+                             "or carry the same word")
+        t, f = [word], [True]
+        for x in words:
+            t += [x, word]
+            f += [False, True]
+        out.append(t)
+        flags.append(f)
+    return out, flags
+
+
+def _check_optional(optional, transcripts):
+    if optional is not None:
+        if len(optional) != len(transcripts):
+            raise ValueError(f"{len(optional)} optional sequences for {len(transcripts)} transcripts")
+        for r, (o, t) in enumerate(zip(optional, transcripts)):
+            if len(o) != len(t):
+                raise ValueError(f"optional[{r}] has {len(o)} entries for a transcript of {len(t)} positions")
+
+
 def train_connected(observations: Sequence[np.ndarray], transcripts: Sequence[Sequence], models: Sequence[HMMTrained],
                     epsilon: float = 1e-6, max_iterations: int = 100, end_final: bool = True, *,
-                    device: Optional[int] = None) -> Tuple[List[HMMTrained], List[Tuple[float, float]]]:
+                    device: Optional[int] = None, optional=None) -> Tuple[List[HMMTrained], List[Tuple[float, float]]]:
     """Embedded re-estimation of word models from connected speech (BaumWelchEngine.embedded_train): recording r
     was spoken as the words transcripts[r], a list of the models' .word names, with no word boundaries given.
     Returns (the re-estimated models, in the order given, and the (L, diff) record of every iteration).  A word no
     transcript names comes back unchanged.  end_final: every recording ends in the last state of its last word, as
-    decode_words assumes by default.  The models must share one shape."""
+    decode_words assumes by default.  optional: one boolean sequence per transcript, True where the position may be
+    passed over (with_optional builds the usual `sil? one sil? two sil?`); a word named only at optional positions
+    that no recording visits comes back unchanged.  The models must share one shape."""
     if len(models) == 0:
         raise ValueError("no word models")
     N, M = int(models[0].states), int(np.asarray(models[0].B).shape[1])
@@ -365,6 +397,7 @@ def train_connected(observations: Sequence[np.ndarray], transcripts: Sequence[Se
     if len(transcripts) != len(observations):
         raise ValueError(f"{len(transcripts)} transcripts for {len(observations)} recordings")
     ids = transcript_ids(transcripts, models)
+    _check_optional(optional, transcripts)
     if len(observations) == 0:
         return list(models), []
     pi = np.stack([np.asarray(h.Pi, dtype=np.float64).reshape(N) for h in models])
@@ -373,7 +406,7 @@ def train_connected(observations: Sequence[np.ndarray], transcripts: Sequence[Se
     with BaumWelchEngine(N, M, device=device) as eng:
         eng.set_observations(list(observations))
         pi, A, B, records, _ = eng.embedded_train(pi, A, B, ids, epsilon=epsilon, max_iterations=max_iterations,
-                                                  end_final=end_final)
+                                                  end_final=end_final, optional=optional)
     return [HMMTrained(states=N, symbols=M, A=A[w], B=B[w], Pi=pi[w], word=h.word) for w, h in enumerate(models)], records
 
 

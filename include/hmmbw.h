@@ -46,7 +46,8 @@ extern "C" {
                                  of version 5: an older library lacks the symbol; hmmbw_mfcc and
                                  hmmbw_mfcc_tables are new entry points of version 5: an older library lacks the
                                  symbols; hmmbw_align is a new entry point of version 5: an older library lacks
-                                 the symbol) */
+                                 the symbol; hmmbw_align_optional and hmmbw_embedded_train_optional are new
+                                 entry points of version 5: an older library lacks the symbols) */
 
 #define HMMBW_OK 0
 #define HMMBW_E_INVALID (-1)        /* bad argument (shape, range, null pointer)             */
@@ -395,6 +396,53 @@ int hmmbw_align(hmmbw_ctx *ctx, int n_words,
                 int flags,
                 double *logp_out, int32_t *path_out, int64_t path_len,
                 int32_t *bounds_out, int64_t bounds_len);
+
+/* Optional transcript positions: hmmbw_align and hmmbw_embedded_train on a chain in which some positions may be
+ * passed over, as in a transcript `sil? one sil? two sil?` for recordings with pauses nobody marked.  `optional`
+ * (HOST) has one byte per transcript position, in the CSR order of word_ids: 1 = a complete path may visit the
+ * position or not, 0 = it must.  NULL means no optional position: the call is then the plain entry point's, kernel
+ * included.  A complete path visits a subset of the positions, in order, that contains every position with
+ * optional = 0; every visited position takes at least one frame and is left from its last state.  So, with
+ * x(m) = the value of (m, N-1) one step earlier:
+ *   entry sources of (l, j): (l-1, N-1), and also (l-2, N-1) if l >= 2 and optional[l-1]; both of weight pi_{w_l}[j]
+ *   start positions:         0, and also 1 if optional[0]
+ *   end positions:           L-1, and also L-2 if optional[L-1]; the END_FINAL rule holds per end position.
+ * An utterance with fewer frames than mandatory positions has no path.  Transcript rules, else HMMBW_E_INVALID:
+ * every flag is 0 or 1, no two adjacent positions are optional, every transcript has a mandatory position (so an
+ * optional position 0 implies L >= 2).  Every other argument, check, error and output is the plain entry point's.
+ *
+ * hmmbw_align_optional: the recursion of hmmbw_align with
+ *   entry_t(l,j) = max(delta_{t-1}(l-1,N-1), delta_{t-1}(l-2,N-1) if optional[l-1]) + log pi_{w_l}[j]
+ *   delta_0(1,j) = log pi_{w_1}[j] + log b_{w_1,j}(o_0) if optional[0].
+ * On any tie the path that skips less wins: the within-word arc beats an entry, as in hmmbw_align; the entry from
+ * l-1 beats the one from l-2 (the two sources are compared before the common weight is added); an end in L-1 beats
+ * one in L-2.  path_out keeps l N + j with l the index in the transcript as given.  bounds_out is -1 for a position
+ * the path passes over (a visited position ends where the next visited one starts), and all -1 where logp is -inf.
+ * With paths the workspace grows by 8 bytes per step and wave: a 64-bit lane mask that says which entry source won
+ * (the nibble word of the back-pointers is full at N = 8).
+ *
+ * hmmbw_embedded_train_optional: the same sums with + for max.  alpha_0 is set on every start position; the entry
+ * term of (l, j) is (x(l-1) + optional[l-1] x(l-2)) pi_{w_l}[j]; beta_t(l, N-1) gains E_{l+1} + optional[l+1] E_{l+2}
+ * with E_m = sum_j pi_{w_m}[j] v_{t+1}(m, j); beta_{T-1} is set on every end position.  entry[w][j] collects gamma_0
+ * on the start positions and the posteriors of both kinds of entry arc; the other sums are defined as in
+ * hmmbw_embedded_train.  The denominator of pi_w is (mandatory instances of w in ALL transcripts) + present[w], where
+ * present[w] is the summed entry mass of the optional instances of w (the probability that the instance is visited)
+ * over the utterances with P_r > 0; without optional positions that is count[w].  A word whose denominator is 0 in
+ * every iteration keeps its parameters bit for bit, whatever `normalise` says.  Multi-rank and deterministic
+ * contexts: HMMBW_E_UNSUPPORTED, as for hmmbw_embedded_train. */
+int hmmbw_align_optional(hmmbw_ctx *ctx, int n_words,
+                         const double *pi, const double *A, const double *B,
+                         const int64_t *word_offsets, const int32_t *word_ids, const uint8_t *optional,
+                         int64_t n_seq, int flags,
+                         double *logp_out, int32_t *path_out, int64_t path_len,
+                         int32_t *bounds_out, int64_t bounds_len);
+int hmmbw_embedded_train_optional(hmmbw_ctx *ctx, int n_words,
+                                  double *pi, double *A, double *B,
+                                  const int64_t *word_offsets, const int32_t *word_ids, const uint8_t *optional,
+                                  int64_t n_seq,
+                                  int flags, double epsilon, int64_t max_iterations, int normalise,
+                                  hmmbw_iter_record *records, int64_t records_cap, int64_t *n_records,
+                                  double *logp_out);
 
 /* Engine knobs.  HMMBW_OPT_SAFE_SCALING = 1 forces the per-step power-of-two normalisation of the
  * forward recursion (default 0: lagged normalisation, automatic per-wave fallback to the per-step
