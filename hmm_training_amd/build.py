@@ -1,8 +1,8 @@
 """Build libhmmbw.so in-tree for gfx950 with hipcc (the driver's build() check runs this on CPU).
 
 The engine is split into translation units that compile in parallel: the host/ABI units, one per
-subsystem and sharing csrc/host.hpp (csrc/hmmbw.hip: context, planner, training and status ABI;
-alloc.hip: block cache and allocation ledger; peer.hip: peer all-reduce; comm.hip: RCCL communicator;
+subsystem and sharing csrc/host.hpp (csrc/hmmbw.hip: context, observations, options, parameters, planner and
+scoring; train.hip: the M-step kernels and the training ABI; status.hip: the status readers; alloc.hip: block cache and allocation ledger; peer.hip: peer all-reduce; comm.hip: RCCL communicator;
 group.hip: grouped launches; viterbi.hip: the Viterbi decoder and its kernels; posterior.hip: the state
 posteriors and their kernels; lbg.hip: LBG codebook training and its kernels; wordnet.hip: connected-word
 decoding and its kernels; embedded.hip: embedded training over transcribed word sequences and its kernels;
@@ -41,8 +41,9 @@ def units():
     wide_flags = ["-mllvm", "-amdgpu-sched-strategy=max-memory-clause"]
     u = [(SRC, [], "hmmbw"), (os.path.join(CSRC, "estep_wide_inst.hip"), wide_flags, "estep_wide"),
          (os.path.join(CSRC, "vq.hip"), [], "vq")]
-    u += [(os.path.join(CSRC, s + ".hip"), [], s) for s in ("alloc", "peer", "comm", "group", "viterbi", "posterior",
-                                                            "lbg", "wordnet", "embedded", "mfcc", "align")]
+    u += [(os.path.join(CSRC, s + ".hip"), [], s) for s in ("train", "status", "alloc", "peer", "comm", "group", "viterbi",
+                                                            "posterior", "lbg", "wordnet", "embedded", "mfcc",
+                                                            "align")]
     u += [(os.path.join(CSRC, "estep_small_inst.hip"), [f"-DHMMBW_INST_N={n}"], f"estep_small_n{n}")
           for n in SMALL_N]
     return u

@@ -162,19 +162,18 @@ int hmmbw_group_iterate(hmmbw_group *g, int64_t n_iter) {
             for (int l = l0; l < l0 + step; ++l)
                 for (int i = 0; i < n; ++i) {
                     hmmbw_ctx *c = g->m[(size_t)i];
-                    if (c->pend.on && !c->can_merge())
-                        if (int rc = flush_mstep(c)) return rc;
-                    const long long e = c->e_count++;
-                    const long long nz = (long long)c->ncopies * c->copy_len();
+                    long long e = 0;
+                    if (int rc = next_estep(c, &e)) return rc;
                     Plan &p = plans[(size_t)l * n + i];
-                    if (int rc = plan_estep(c, false, c->state(), c->copies(e), c->llpart(e), c->copies(e + 1), nz,
-                                            true, &p, nullptr, 0, false))
-                        return rc;
+                    // allow_join = false: a grouped kernel never runs the joined map
+                    if (int rc = plan_estep(c, c->io_local(e), false, &p)) return rc;
                     if (!p.gfn || p.gfn != plans[0].gfn || p.block != kBlock)
                         return fail(HMMBW_E_UNSUPPORTED, "group members need the same grouped kernel");
-                    if (p.flip) c->scur ^= 1;  // slots are read by the launch through the plan's pointers
-                    // a grouped kernel exists only outside the deterministic mode and never runs the joined
-                    // map (allow_join = false above): ncopies sources, a pair per workgroup
+                    // planned here, enqueued later: the launch reads the slots through the plan's pointers, so
+                    // the flip a context's own launch does when it is enqueued is this loop's
+                    if (p.flip) c->scur ^= 1;
+                    // map.nblocks, not last_nll (which only a context's own launch sets): without the joined map
+                    // and outside the deterministic mode, ncopies sources and a pair per workgroup
                     pend_local(c, e, c->map.nblocks);
                 }
             if (step == nl) {
@@ -199,8 +198,7 @@ int hmmbw_group_score(hmmbw_group *g, double *out) {
     for (int i = 0; i < n; ++i) {
         hmmbw_ctx *c = g->m[(size_t)i];
         if (int rc = flush_mstep(c)) return rc;
-        if (int rc = plan_estep(c, true, nullptr, nullptr, nullptr, nullptr, 0, false, &plans[(size_t)i]))
-            return rc;
+        if (int rc = plan_score(c, &plans[(size_t)i])) return rc;
         if (!plans[(size_t)i].gfn || plans[(size_t)i].gfn != plans[0].gfn)
             return fail(HMMBW_E_UNSUPPORTED, "group members need the same grouped kernel");
     }

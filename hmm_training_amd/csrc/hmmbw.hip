@@ -27,59 +27,32 @@
 //   k_estep_mfma<NT,FWD_ONLY,DET,WQ>       16 < N <= 64: a workgroup owns a tile of 16 sequences, wave m
 //        the 16-state block m; the recursions and xi on the fp64 MFMA, the other waves' blocks through
 //        LDS (estep_mfma.hpp).  k_bnum_gather sums its gamma rows per symbol into the B numerator.
+//   k_det_reduce    (deterministic mode) sum the per-workgroup partial statistics in workgroup order: a
+//                   follow-up of the E-step launch, as k_bnum_gather is (enqueue_plan).
+//   k_finalise      the reference's return-path normalisation (:524-541).
+//   train.hip:
 //   k_reduce_local  (multi-rank) sum the statistics copies into the all-reduce buffer + the rank's
 //                   (max, sum exp) pair of log P_r.
-//   k_det_reduce    (deterministic mode) sum the per-workgroup partial statistics in workgroup order.
 //   k_mstep / k_mstep_staged  one workgroup: L, M-step, convergence record, zero the statistics
 //                   (staged: all statistics gathered into LDS with one batch of loads).
 //   k_mstep_grid    large N x K (wide path): B re-estimated by the whole grid, the rest by workgroup 0.
 //                   (Their bodies: mstep.hpp; merged into the next E-step launch: merged_mstep.)
-//   k_snapshot      the state and the iteration records into pinned host memory (hmmbw_status_post).
-//   k_finalise  the reference's return-path normalisation (:524-541).
 //   k_init_state    the convergence state of a new run.
+//   status.hip:
+//   k_snapshot      the state and the iteration records into pinned host memory (hmmbw_status_post).
 //   (peer.hip, viterbi.hip and vq.hip hold their own kernels.)
 //
 // Host units (host.hpp): this one holds the context's life cycle, observations, options and parameters,
-// the launch planner, hmmbw_estep / _mstep / _iterate*, status, scoring and timing; alloc.hip the block
-// cache and the allocation ledger, peer.hip the peer all-reduce (kernels included), comm.hip the RCCL
-// communicator, group.hip the grouped launches, viterbi.hip the Viterbi decoder.
-#include <atomic>
+// the launch planner (plan_estep / plan_score and their launches), scoring, timing and hmmbw_vq_encode;
+// train.hip the M-step, the pending M-step and hmmbw_reset_training / _estep / _mstep / _iterate*, status.hip
+// the status readers, alloc.hip the block cache and the allocation ledger, peer.hip the peer all-reduce (kernels
+// included), comm.hip the RCCL communicator, group.hip the grouped launches, viterbi.hip the Viterbi decoder.
 #include <map>
 #include <mutex>
 
 #include "host.hpp"
-#include "mstep.hpp"
 
 namespace hmmbw {
-
-// Multi-rank: sum this rank's statistics copies into the caller's buffer (for the all-reduce),
-// zero the copies, and write the rank's (max, sum exp) pair of log P into its slot.
-__global__ void __launch_bounds__(256) k_reduce_local(double *copies, int ncopies, long long copy_len,
-                                                      const double *llpart, long long nblocks, double *stats,
-                                                      long long off_ll, int world, int rank,
-                                                      const IterState *state) {
-    __shared__ double sh[16];
-    if (state->done) return;
-    for (long long idx = (long long)blockIdx.x * blockDim.x + threadIdx.x; idx < copy_len;
-         idx += (long long)gridDim.x * blockDim.x) {
-        double v = 0.0;
-        for (int c = 0; c < ncopies; ++c) {
-            v += copies[c * copy_len + idx];
-            copies[c * copy_len + idx] = 0.0;
-        }
-        stats[idx] = v;
-    }
-    if (blockIdx.x == 0) {
-        double m, s;
-        combine_ll_pairs(llpart, nblocks, sh, &m, &s);
-        if (threadIdx.x < 2 * world) stats[off_ll + threadIdx.x] = 0.0;
-        __syncthreads();
-        if (threadIdx.x == 0) {
-            stats[off_ll + 2 * rank] = (s > 0.0) ? m : 0.0;
-            stats[off_ll + 2 * rank + 1] = s;
-        }
-    }
-}
 
 // Deterministic mode: sum the per-workgroup partial statistics [blocks][n] in workgroup order.
 __global__ void __launch_bounds__(256) k_det_reduce(const double *part, long long nblocks, long long n, double *out,
@@ -90,37 +63,6 @@ __global__ void __launch_bounds__(256) k_det_reduce(const double *part, long lon
         for (long long b = 0; b < nblocks; ++b) v += part[b * n + i];
         out[i] = v;
     }
-}
-
-__global__ void __launch_bounds__(256) k_mstep(MArgs m) {
-    if (carry_if_done(m)) return;
-    mstep_block(m);
-}
-
-__global__ void __launch_bounds__(256) k_mstep_grid(MArgs m) {
-    if (carry_if_done(m)) return;
-    mstep_grid(m);
-}
-
-// single-rank M-step with the statistics staged in dynamic LDS (copy_len doubles)
-__global__ void __launch_bounds__(256) k_mstep_staged(MArgs m) {
-    extern __shared__ double sSt[];
-    if (carry_if_done(m)) return;
-    mstep_staged(m, sSt);
-}
-
-// Status snapshot for hmmbw_status_post: the state record and the iteration records [first, iteration)
-// written straight into pinned host memory (one small launch on the stream instead of DMA copies).
-__global__ void __launch_bounds__(256) k_snapshot(const IterState *st, const double *hist, long long first,
-                                                   IterState *hst, double *hrec) {
-    const IterState s = *st;
-    const long long n = min(max(s.iteration - first, 0LL), (long long)kHist);
-    for (long long i = threadIdx.x; i < n; i += blockDim.x) {
-        const long long k = (first + i) % kHist;
-        hrec[2 * i] = hist[2 * k];
-        hrec[2 * i + 1] = hist[2 * k + 1];
-    }
-    if (threadIdx.x == 0) *hst = s;
 }
 
 // safe_exp + normalisation of the returned parameters (:524-541)
@@ -140,19 +82,6 @@ __global__ void k_finalise(const double *pi, const double *A, const double *B, i
         for (int k = 0; k < K; ++k) sb += B[(long long)i * K + k];
         for (int k = 0; k < K; ++k) oB[(long long)i * K + k] = sb > 0.0 ? B[(long long)i * K + k] / sb : B[(long long)i * K + k];
     }
-}
-
-__global__ void k_init_state(IterState *st, double eps, long long max_it) {
-    st->prev_L = -INFINITY;
-    st->last_L = -INFINITY;
-    st->last_diff = INFINITY;
-    st->epsilon = eps;
-    st->iteration = 0;
-    st->max_iterations = max_it;
-    st->done = max_it <= 0 ? 1 : 0;
-    st->converged = 0;
-    st->error = 0;
-    st->error_src = 0;
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -276,6 +205,7 @@ static int realloc_stats(hmmbw_ctx *c) {
     return HMMBW_OK;
 }
 
+// what a launch's arguments take from the context; where it reads and writes is the EstepIo's (plan_launch)
 static EArgs make_eargs(hmmbw_ctx *c) {
     EArgs a{};
     a.L = Layout{c->d_sym, c->d_wsym, c->d_wckoff, c->d_wspoff, c->d_wT, c->d_wfull, c->d_slen, c->d_sseq,
@@ -289,14 +219,10 @@ static EArgs make_eargs(hmmbw_ctx *c) {
     a.part = c->d_part;
     a.spack = c->d_sp;
     a.ebuf = c->d_ebuf;
-    a.copies = c->copies(0);
     a.copy_len = c->copy_len();
-    a.ncopies = c->ncopies;
     a.logp = c->d_logp;
-    a.llpart = c->llpart(0);
     a.force_safe = c->force_safe;
     a.ablate = c->ablate;
-    a.state = c->state();
     a.K = c->K;
     a.N = c->N;
     a.off_S = c->off_S();
@@ -307,90 +233,6 @@ static EArgs make_eargs(hmmbw_ctx *c) {
     a.xact = c->map.xact;
     a.prio = c->prio >= 0 ? c->prio : (c->topo == HMMBW_TOPOLOGY_LEFT_TO_RIGHT ? 2 : 0);
     return a;
-}
-
-// M-step arguments for the pending statistics: this context's copies (single rank) or the caller's
-// all-reduced buffer with one (max, sum exp) pair per rank
-static MArgs make_margs(hmmbw_ctx *c, const hmmbw_ctx::Pending &p) {
-    MArgs m{};
-    m.src = p.src;
-    m.zero_ll = p.local ? nullptr : const_cast<double *>(p.ll);
-    m.nsrc = p.nsrc;
-    m.copy_len = c->copy_len();
-    m.pi = c->d_pi;
-    m.A = c->d_A;
-    m.B = c->d_B;
-    m.Bt = c->d_Bt;
-    m.llpart = p.ll;
-    m.nblocks = p.nll;
-    m.R_global = p.R;
-    m.state = c->state();
-    m.state_out = c->d_state + (c->scur ^ 1);
-    m.hist = c->d_hist;
-    m.N = c->N;
-    m.K = c->K;
-    m.G = c->G;
-    m.world = c->world;
-    m.local_lse = p.local ? 1 : 0;
-    m.bt_perm = c->wide ? 1 : 0;
-    m.off_S = c->off_S();
-    m.off_gex = c->off_gex();
-    m.off_gall = c->off_gall();
-    m.live = c->h_live;
-    m.live_epoch = c->live_epoch;
-    m.off_bnum = c->off_bnum();
-    m.off_ll = c->off_ll();
-    return m;
-}
-
-// run the pending M-step as its own one-workgroup kernel
-int flush_mstep(hmmbw_ctx *c) {
-    if (!c->pend.on) return HMMBW_OK;
-    c->pend.on = false;
-    if (c->ablate & 4) return HMMBW_OK;  // diagnostics (HMMBW_OPT_ABLATE bit 2): no separate M-step kernel
-    const MArgs m = make_margs(c, c->pend);
-    const size_t staged = sizeof(double) * (size_t)c->copy_len();
-    const long long nb = (long long)c->N * c->K;
-    if (m.local_lse && staged <= 64 * 1024 && c->N * c->N <= 256)
-        hipLaunchKernelGGL(k_mstep_staged, dim3(1), dim3(256), staged, c->stream, m);
-    else if (nb > 8192)  // large B: the whole grid re-estimates it (one workgroup took 150 us at 64 x 1024)
-        hipLaunchKernelGGL(k_mstep_grid, dim3((unsigned)std::min<long long>((nb + 1023) / 1024, 256)), dim3(256), 0,
-                           c->stream, m);
-    else
-        hipLaunchKernelGGL(k_mstep, dim3(1), dim3(256), 0, c->stream, m);
-    HIP_TRY(hipGetLastError());
-    c->scur ^= 1;
-    return HMMBW_OK;
-}
-
-// The pending M-step reads this context's statistics of E-step launch e (single rank); nll: the
-// log-likelihood pairs that launch wrote.
-void pend_local(hmmbw_ctx *c, long long e, long long nll) {
-    hmmbw_ctx::Pending &p = c->pend;
-    p.on = true;
-    p.local = true;
-    p.src = c->copies(e);
-    p.nsrc = c->det ? 1 : c->ncopies;
-    p.ll = c->llpart(e);
-    p.nll = nll;
-    p.ext = nullptr;
-    p.R = c->R;
-}
-
-// The pending M-step reads an all-reduced buffer: nsrc statistics copies, then one (max, sum exp) pair per
-// rank (copy_len() == off_ll(), so the packed statistics of hmmbw_mstep are the nsrc = 1 case).
-// Deferred into the next E-step launch when that can merge it; queries flush it.
-static int pend_reduced(hmmbw_ctx *c, double *src, int nsrc, long long R) {
-    hmmbw_ctx::Pending &p = c->pend;
-    p.on = true;
-    p.local = false;
-    p.src = src;
-    p.nsrc = nsrc;
-    p.ll = src + (long long)nsrc * c->copy_len();
-    p.nll = c->world;
-    p.ext = src;
-    p.R = R;
-    return c->can_merge() ? HMMBW_OK : flush_mstep(c);
 }
 
 // The largest dynamic LDS each kernel has been allowed so far on each device: hipFuncSetAttribute once
@@ -464,21 +306,20 @@ static int ensure_wq(hmmbw_ctx *c) {
     return HMMBW_OK;
 }
 
-// E-step launch e accumulates into copies and llpart; it clears `zero` (zero_len doubles) and, when
-// `merge` is set, first runs the pending M-step in its prologue (which consumes c->pend).
-int plan_estep(hmmbw_ctx *c, bool fwd_only, const IterState *state, double *copies, double *llpart, double *zero,
-               long long zero_len, bool merge, Plan *P, double *rank_ll, int ncopies, bool allow_join) {
+// Resolve the kernel, the grid and the arguments of a training (plan_estep) or scoring (plan_score) launch.  A
+// training launch first runs the pending M-step in its prologue when that can merge (which consumes c->pend).
+static int plan_launch(hmmbw_ctx *c, bool fwd_only, const EstepIo &io, bool allow_join, Plan *P) {
     Plan &p = *P;
     p = Plan{};
     EArgs &a = p.a;
     a = make_eargs(c);
-    a.state = state;
-    if (ncopies > 0) a.ncopies = ncopies;
-    if (copies) a.copies = copies;
-    if (llpart) a.llpart = llpart;
-    a.zero = zero;
-    a.zero_len = zero ? zero_len : 0;
-    a.rank_ll = rank_ll;
+    a.state = io.state;
+    a.ncopies = io.ncopies;
+    a.copies = io.copies;
+    a.llpart = io.llpart;
+    a.zero = io.zero;
+    a.zero_len = io.zero ? io.zero_len : 0;
+    a.rank_ll = io.rank_ll;
     a.done_ctr = c->d_ctr;
     const int wpb = kBlock / kWave;
     p.grid = (unsigned)c->map.nblocks;
@@ -534,7 +375,7 @@ int plan_estep(hmmbw_ctx *c, bool fwd_only, const IterState *state, double *copi
             }
         }
     }
-    if (p.grid > 0 && merge && !fwd_only && c->pend.on && c->can_merge()) {
+    if (p.grid > 0 && !fwd_only && c->pend.on && c->can_merge()) {
         a.merged = 1;
         a.m = make_margs(c, c->pend);
         c->pend.on = false;
@@ -543,10 +384,17 @@ int plan_estep(hmmbw_ctx *c, bool fwd_only, const IterState *state, double *copi
     return HMMBW_OK;
 }
 
-int launch_estep(hmmbw_ctx *c, bool fwd_only, const IterState *state, double *copies, double *llpart, double *zero,
-                 long long zero_len, bool merge, double *rank_ll, int ncopies) {
-    Plan p;
-    if (int rc = plan_estep(c, fwd_only, state, copies, llpart, zero, zero_len, merge, &p, rank_ll, ncopies)) return rc;
+int plan_estep(hmmbw_ctx *c, const EstepIo &io, bool allow_join, Plan *P) {
+    return plan_launch(c, false, io, allow_join, P);
+}
+
+// forward only: no state to read and no statistics to keep; the arguments carry the first buffer of each kind
+int plan_score(hmmbw_ctx *c, Plan *P) {
+    return plan_launch(c, true, EstepIo{nullptr, c->copies(0), c->llpart(0), nullptr, 0, nullptr, c->ncopies}, true, P);
+}
+
+// enqueue a context's own launch, with its follow-up kernels and its timing events
+static int enqueue_plan(hmmbw_ctx *c, bool fwd_only, const Plan &p) {
     if (p.grid == 0) return HMMBW_OK;
     const EArgs &a = p.a;
     const bool timed = c->timing && !fwd_only && (c->timing_seq++ % c->timing) == 0;
@@ -587,8 +435,20 @@ int launch_estep(hmmbw_ctx *c, bool fwd_only, const IterState *state, double *co
     return HMMBW_OK;
 }
 
+int launch_estep(hmmbw_ctx *c, const EstepIo &io) {
+    Plan p;
+    if (int rc = plan_estep(c, io, true, &p)) return rc;
+    return enqueue_plan(c, false, p);
+}
+
+int launch_score(hmmbw_ctx *c) {
+    Plan p;
+    if (int rc = plan_score(c, &p)) return rc;
+    return enqueue_plan(c, true, p);
+}
+
 // the E-step pairs, and the mid events' share of theirs (hmmbw_timing_split)
-static int drain_timing(hmmbw_ctx *c) {
+int drain_timing(hmmbw_ctx *c) {
     for (size_t i = 0; i < c->mid_pending.size(); ++i) {
         hipEvent_t em = c->mid_pending[i];
         if (!em) continue;
@@ -622,15 +482,6 @@ static void resolve_topology(hmmbw_ctx *c) {
         t = lr ? HMMBW_TOPOLOGY_LEFT_TO_RIGHT : HMMBW_TOPOLOGY_DENSE;
     }
     c->topo = t;
-}
-
-// message of a device-side stop (IterState::error, set with done by a bounded wait that expired)
-static std::string device_error(const IterState &h) {
-    if (h.error_src == kErrWorkQueue)
-        return "EM stopped on a device-side failure: a wide work-queue backward sweep did not see its tile's "
-               "forward sweep finish within HMMBW_OPT_WQ_TIMEOUT_MS";
-    return "EM stopped on a device-side failure: a rank did not deliver its statistics to the peer all-reduce "
-           "within HMMBW_OPT_PEER_TIMEOUT_MS";
 }
 
 }  // namespace hmmbw
@@ -726,8 +577,8 @@ int hmmbw_ctx_create(int device, int n_states, int n_symbols, hmmbw_ctx **out) {
     }
     if (!rc) rc = realloc_stats(c);
     if (!rc) {
-        hipLaunchKernelGGL(k_init_state, dim3(1), dim3(1), 0, c->stream, c->d_state, 0.0, 0LL);
-        hipLaunchKernelGGL(k_init_state, dim3(1), dim3(1), 0, c->stream, c->d_state + 1, 0.0, 0LL);
+        init_state(c, c->d_state, 0.0, 0);
+        init_state(c, c->d_state + 1, 0.0, 0);
         hipError_t e = hipStreamSynchronize(c->stream);
         if (e != hipSuccess) rc = fail(HMMBW_E_HIP, std::string("init: ") + hipGetErrorString(e));
     }
@@ -747,13 +598,8 @@ int hmmbw_ctx_destroy(hmmbw_ctx *c) {
     // once (hipFree used to synchronise the device implicitly)
     (void)hipDeviceSynchronize();
     dfree(c->d_pi); dfree(c->d_A); dfree(c->d_B); dfree(c->d_Bt); dfree(c->d_out);
-    for (auto &sn : c->snaps) {
-        if (sn.ev) (void)hipEventDestroy(sn.ev);
-        cached_free(sn.st, kPinnedBlock);
-        cached_free(sn.hist, kPinnedBlock);
-    }
+    status_free(c);
     dfree(c->d_state); dfree(c->d_hist); dfree(c->d_copies); dfree(c->d_ext); dfree(c->d_xbuf); dfree(c->d_ctr);
-    cached_free(c->h_live, kPinnedBlock);
     comm_destroy(c);
     peer_destroy(c);
     free_obs(c);
@@ -960,24 +806,7 @@ int hmmbw_set_option(hmmbw_ctx *c, int key, int64_t value) {
         return HMMBW_OK;
     }
     if (key == HMMBW_OPT_LIVE_STATUS) {
-        if (int rc = set_device(c)) return rc;
-        HIP_TRY(hipStreamSynchronize(c->stream));  // no launch of the old setting is still in flight
-        if (value == 0) {
-            cached_free(c->h_live, kPinnedBlock);
-            c->h_live = nullptr;
-            return HMMBW_OK;
-        }
-        if (c->h_live) return HMMBW_OK;
-        HIP_TRY(cached_alloc(reinterpret_cast<void **>(&c->h_live), sizeof(LiveBlock), kPinnedBlock));
-        // seed the mirror with the state as it stands (records of a pending M-step follow when it runs)
-        IterState h{};
-        HIP_TRY(hipMemcpy(&h, c->state(), sizeof(IterState), hipMemcpyDeviceToHost));
-        HIP_TRY(hipMemcpy(c->h_live->hist, c->d_hist, sizeof(double) * 2 * (size_t)kHist, hipMemcpyDeviceToHost));
-        c->h_live->slot[h.iteration & 1] = h;
-        std::atomic_thread_fence(std::memory_order_release);
-        reinterpret_cast<volatile unsigned long long &>(c->h_live->pub) =
-            ((unsigned long long)c->live_epoch << 32) | (unsigned long long)(unsigned)h.iteration;
-        return HMMBW_OK;
+        return live_status_set(c, value != 0);
     }
     if (key == HMMBW_OPT_WQ_TIMEOUT_MS) {
         if (value < 0) return fail(HMMBW_E_INVALID, "work-queue timeout must be >= 0 ms");
@@ -1060,367 +889,9 @@ int hmmbw_set_params(hmmbw_ctx *c, const double *pi, const double *A, const doub
     return ensure_zf(c);
 }
 
-int hmmbw_reset_training(hmmbw_ctx *c, double epsilon, int64_t max_iterations) {
-    if (!c) return fail(HMMBW_E_INVALID, "null context");
-    if (int rc = check_closed(c)) return rc;
-    if (int rc = set_device(c)) return rc;
-    if (int rc = flush_mstep(c)) return rc;
-    hipLaunchKernelGGL(k_init_state, dim3(1), dim3(1), 0, c->stream, c->state(), epsilon, (long long)max_iterations);
-    HIP_TRY(hipGetLastError());
-    ++c->live_epoch;  // the mirror's records of the previous run no longer count (hmmbw_status_live_wait)
-    HIP_TRY(hipMemsetAsync(c->d_copies, 0, sizeof(double) * 3 * c->ncopies * c->copy_len(), c->stream));
-    if (c->d_xbuf) HIP_TRY(hipMemsetAsync(c->d_xbuf, 0, sizeof(double) * 3 * (size_t)c->xlen, c->stream));
-    // the work queue's counters and flags: a run stopped by a work-queue timeout leaves them armed (the
-    // workgroups that start after the stop return at once and never reach the re-arm)
-    if (c->d_wq) HIP_TRY(hipMemsetAsync(c->d_wq, 0, sizeof(unsigned) * ((size_t)c->map.nblocks + 2), c->stream));
-    // the fused multi-rank completion counter: workgroups that start after a device-side stop return
-    // before counting their log-likelihood pair, so a stopped launch leaves it part-way; the next run's
-    // last-workgroup fold must start from zero
-    HIP_TRY(hipMemsetAsync(c->d_ctr, 0, sizeof(int), c->stream));
-    c->e_count = 0;
-    c->armed = true;
-    return HMMBW_OK;
-}
-
 int hmmbw_stats_len(const hmmbw_ctx *c, int64_t *n) {
     if (!c || !n) return fail(HMMBW_E_INVALID, "null argument");
     *n = c->stats_len();
-    return HMMBW_OK;
-}
-
-int hmmbw_estep(hmmbw_ctx *c, double *stats_dev) {
-    if (int rc = check_ready(c, true)) return rc;
-    if (int rc = check_closed(c)) return rc;
-    if (!stats_dev) return fail(HMMBW_E_INVALID, "null stats buffer");
-    if (c->pend.on && !c->can_merge())
-        if (int rc = flush_mstep(c)) return rc;
-    const long long e = c->e_count++;
-    double *llp = c->llpart(e);
-    // multi-rank: one copy set, cleared by k_reduce_local
-    if (int rc = launch_estep(c, false, c->state(), c->copies(0), llp, nullptr, 0, true)) return rc;
-    const long long n = c->copy_len();
-    const unsigned grid = (unsigned)std::min<long long>((n + 255) / 256, 64);
-    hipLaunchKernelGGL(k_reduce_local, dim3(grid), dim3(256), 0, c->stream, c->copies(0), c->det ? 1 : c->ncopies, n, llp,
-                       c->last_nll, stats_dev, c->off_ll(), c->world, c->rank, c->state());
-    HIP_TRY(hipGetLastError());
-    return HMMBW_OK;
-}
-
-int hmmbw_mstep(hmmbw_ctx *c, double *stats_dev, int64_t n_seq_global) {
-    if (int rc = check_ready(c, true)) return rc;
-    if (int rc = check_closed(c)) return rc;
-    if (!stats_dev) return fail(HMMBW_E_INVALID, "null stats buffer");
-    if (int rc = flush_mstep(c)) return rc;
-    return pend_reduced(c, stats_dev, 1, n_seq_global);
-}
-
-// First half of one multi-rank EM iteration: this rank's E-step, leaving in *buf (*len doubles, device
-// memory of the context) the partial statistics that every rank must all-reduce (sum) before mr_end.
-// Small kernels: fused (the E-step accumulates straight into a triple-buffered all-reduce buffer and
-// its last workgroup writes the rank's (max, sum exp) pair; no k_reduce_local launch).  Wide and
-// deterministic paths: hmmbw_estep + k_reduce_local into d_ext.  The layout is rank-independent: every
-// rank all-reduces the same buffer shape, also a rank whose shard is empty.
-static int mr_begin(hmmbw_ctx *c, long long n_seq_global, double **buf, long long *len) {
-    if (int rc = check_closed(c)) return rc;
-    const bool fused = !c->det;  // the small and the wide E-step accumulate into the all-reduce buffer
-    if (fused) {
-        // rounded to 256 B so all three buffers keep the copies' alignment (a 16-B shift splits the
-        // B-numerator rows' 64-B segments over two cache lines; ~0.7 us per launch at cfg3)
-        const int nc = c->xcopies();
-        const long long xl = c->ar_payload();
-        if (c->xlen != xl) {
-            if (int rc = flush_mstep(c)) return rc;
-            // the caller may still read or write the old buffer on its own stream (its all-reduce)
-            HIP_TRY(hipDeviceSynchronize());
-            dfree(c->d_xbuf);
-            if (int rc = dalloc(&c->d_xbuf, 3 * (size_t)xl)) return rc;
-            HIP_TRY(hipMemsetAsync(c->d_xbuf, 0, sizeof(double) * 3 * (size_t)xl, c->stream));
-            c->xlen = xl;
-            c->e_count = 0;
-        }
-        if (c->pend.on && !c->can_merge())
-            if (int rc = flush_mstep(c)) return rc;
-        const long long e = c->e_count++;
-        double *X = c->d_xbuf + (e % 3) * c->xlen, *Xn = c->d_xbuf + ((e + 1) % 3) * c->xlen;
-        const long long ll_off = (long long)nc * c->copy_len();
-        // accumulate into X (the merged M-step reads the previous, all-reduced X), clear the next
-        if (c->map.nblocks > 0) {
-            if (int rc = launch_estep(c, false, c->state(), X, c->llpart(e), Xn, c->xlen, true,
-                                      X + ll_off + 2LL * c->rank, nc))
-                return rc;
-        } else {  // empty shard: contribute zeros (no E-step launch clears the buffers)
-            HIP_TRY(hipMemsetAsync(X, 0, sizeof(double) * (size_t)c->xlen, c->stream));
-        }
-        *buf = X;
-        *len = c->xlen;
-    } else {
-        if (c->ext_len != c->stats_len()) {  // sized by the world of hmmbw_set_rank
-            if (int rc = flush_mstep(c)) return rc;
-            HIP_TRY(hipStreamSynchronize(c->stream));
-            dfree(c->d_ext);
-            if (int rc = dalloc(&c->d_ext, (size_t)c->stats_len())) return rc;
-            HIP_TRY(hipMemsetAsync(c->d_ext, 0, sizeof(double) * (size_t)c->stats_len(), c->stream));
-            c->ext_len = c->stats_len();
-        }
-        if (int rc = hmmbw_estep(c, c->d_ext)) return rc;
-        *buf = c->d_ext;
-        *len = c->ext_len;
-    }
-    c->ar_open = true;
-    c->ar_fused = fused;
-    c->ar_cur = *buf;
-    c->ar_R = n_seq_global;
-    return HMMBW_OK;
-}
-
-// Second half: the M-step from the all-reduced buffer (merged into the next E-step launch when it can).
-static int mr_end(hmmbw_ctx *c) {
-    if (!c->ar_open) return fail(HMMBW_E_STATE, "no open iteration (hmmbw_iterate_begin first)");
-    c->ar_open = false;
-    if (!c->ar_fused) return hmmbw_mstep(c, c->ar_cur, c->ar_R);
-    return pend_reduced(c, c->ar_cur, c->xcopies(), c->ar_R);
-}
-
-int hmmbw_iterate_begin(hmmbw_ctx *c, int64_t n_seq_global, double **buf, int64_t *n_doubles) {
-    if (int rc = check_ready(c, true)) return rc;
-    if (!buf || !n_doubles) return fail(HMMBW_E_INVALID, "null argument");
-    if (n_seq_global < 0) return fail(HMMBW_E_INVALID, "negative sequence count");
-    if (c->ar_kind == HMMBW_ALLREDUCE_PEER && !c->peer_mode()) return fail(HMMBW_E_STATE, peer_off_msg(c));
-    long long len = 0;
-    if (int rc = mr_begin(c, n_seq_global, buf, &len)) return rc;
-    if (c->peer_mode()) {  // the whole exchange is the engine's: push now, wait + sum in _end
-        if (int rc = peer_push(c, *buf, len)) {
-            c->ar_open = false;
-            return rc;
-        }
-        c->ar_len_last = len;
-    }
-    *n_doubles = len;
-    return HMMBW_OK;
-}
-
-int hmmbw_iterate_end(hmmbw_ctx *c) {
-    if (int rc = check_ready(c, true)) return rc;
-    if (c->ar_open && c->peer_mode())
-        if (int rc = peer_reduce(c)) {
-            c->ar_open = false;
-            return rc;
-        }
-    return mr_end(c);
-}
-
-int hmmbw_allreduce_kind(const hmmbw_ctx *c, int *kind) {
-    if (!c || !kind) return fail(HMMBW_E_INVALID, "null argument");
-    if (c->peer_mode()) *kind = HMMBW_ALLREDUCE_PEER;
-    else if (c->world > 1 || c->comm) *kind = HMMBW_ALLREDUCE_RCCL;
-    else *kind = -1;
-    return HMMBW_OK;
-}
-
-int hmmbw_iterate(hmmbw_ctx *c, int64_t n_iter) {
-    if (int rc = check_ready(c, true)) return rc;
-    if (int rc = check_closed(c)) return rc;
-    if (c->world != 1 || c->comm || c->peer_mode()) {
-        // multi-rank with the engine's own all-reduce: estep -> ncclAllReduce (this stream) or the peer
-        // push / wait + sum -> mstep
-        const bool peer = c->peer_mode();
-        if (c->ar_kind == HMMBW_ALLREDUCE_PEER && !peer) return fail(HMMBW_E_STATE, peer_off_msg(c));
-        if (!peer && !c->comm)
-            return fail(HMMBW_E_STATE, "multi-rank hmmbw_iterate needs hmmbw_comm_init or the peer all-reduce "
-                                       "(or use hmmbw_iterate_begin / all-reduce / _end)");
-        if (!peer)
-            if (int rc = hmmbw_comm_probe(nullptr)) return rc;
-        for (int64_t i = 0; i < n_iter; ++i) {
-            double *ar = nullptr;
-            long long ar_len = 0;
-            if (int rc = mr_begin(c, c->R_global, &ar, &ar_len)) return rc;
-            // between mr_begin and mr_end: any failure closes the iteration again, or every later
-            // training call would fail with HMMBW_E_STATE
-            auto collective = [&]() -> int {
-                const bool timed = c->timing && (c->ar_seq++ % c->timing) == 0;
-                if (timed)
-                    if (int rc = c->ar_timed.take(c->stream)) return rc;
-                // also at world 1 (RCCL's in-place 1-rank sum is a copy kernel, ~2 us): the 1-rank
-                // communicator tests then exercise the same ncclAllReduce call as an 8-GPU run
-                c->ar_len_last = ar_len;
-                if (peer) {
-                    if (int rc = peer_allreduce(c, ar, ar_len)) return rc;
-                } else {
-                    if (int rc = comm_allreduce(c, ar, ar_len)) return rc;
-                }
-                if (timed) {
-                    if (int rc = c->ar_timed.done(c->stream)) return rc;
-                    if (c->ar_timed.pending.size() >= 256)
-                        if (int rc = c->ar_timed.drain()) return rc;
-                }
-                return HMMBW_OK;
-            };
-            if (int rc = collective()) {
-                c->ar_open = false;
-                return rc;
-            }
-            if (int rc = mr_end(c)) return rc;
-        }
-        return HMMBW_OK;
-    }
-    const long long nz = (long long)c->ncopies * c->copy_len();
-    for (int64_t i = 0; i < n_iter; ++i) {
-        if (c->pend.on && !c->can_merge())
-            if (int rc = flush_mstep(c)) return rc;
-        const long long e = c->e_count++;
-        // statistics triple buffer: this launch adds into e, the merged M-step reads e - 1, and e + 1
-        // (read by launch e - 2) is cleared for the next launch
-        if (int rc = launch_estep(c, false, c->state(), c->copies(e), c->llpart(e), c->copies(e + 1), nz, true))
-            return rc;
-        pend_local(c, e, c->last_nll);
-        if (!c->can_merge())
-            if (int rc = flush_mstep(c)) return rc;
-        if (c->timing && c->timed.pending.size() >= 256)
-            if (int rc = drain_timing(c)) return rc;
-    }
-    return HMMBW_OK;
-}
-
-static void fill_status(const IterState &h, hmmbw_status *st) {
-    st->iterations = h.iteration;
-    st->done = h.done;
-    st->converged = h.converged;
-    st->last_log_likelihood = h.last_L;
-    st->last_diff = h.last_diff;
-}
-
-int hmmbw_get_status(hmmbw_ctx *c, hmmbw_status *st, hmmbw_iter_record *rec, int64_t first, int64_t count) {
-    if (!c || !st) return fail(HMMBW_E_INVALID, "null argument");
-    if (int rc = set_device(c)) return rc;
-    if (int rc = flush_mstep(c)) return rc;
-    IterState h{};
-    HIP_TRY(hipMemcpyAsync(&h, c->state(), sizeof(IterState), hipMemcpyDeviceToHost, c->stream));
-    std::vector<double> hist(2 * (size_t)kHist);
-    if (rec && count > 0)
-        HIP_TRY(hipMemcpyAsync(hist.data(), c->d_hist, sizeof(double) * hist.size(), hipMemcpyDeviceToHost, c->stream));
-    HIP_TRY(hipStreamSynchronize(c->stream));
-    fill_status(h, st);
-    if (h.error) return fail(h.error, device_error(h));
-    if (rec && count > 0) {
-        if (first < 0 || first + count > h.iteration || first < h.iteration - kHist)
-            return fail(HMMBW_E_INVALID, "requested iteration records are not available");
-        for (int64_t i = 0; i < count; ++i) {
-            const int64_t k = (first + i) % kHist;
-            rec[i].log_likelihood = hist[2 * k];
-            rec[i].diff = hist[2 * k + 1];
-        }
-    }
-    return HMMBW_OK;
-}
-
-int hmmbw_status_post(hmmbw_ctx *c, int64_t first, int64_t *ticket) {
-    if (!c || !ticket) return fail(HMMBW_E_INVALID, "null argument");
-    if (first < 0) return fail(HMMBW_E_INVALID, "negative first iteration");
-    if (int rc = set_device(c)) return rc;
-    hmmbw_ctx::Snap &sn = c->snaps[c->snap_next % 2];
-    if (!sn.ev) {
-        HIP_TRY(hipEventCreateWithFlags(&sn.ev, hipEventDisableTiming));
-        // fine-grained host memory the snapshot kernel writes (visible once its event has completed)
-        HIP_TRY(cached_alloc(reinterpret_cast<void **>(&sn.st), sizeof(IterState), kPinnedBlock));
-        HIP_TRY(cached_alloc(reinterpret_cast<void **>(&sn.hist), sizeof(double) * 2 * (size_t)kHist, kPinnedBlock));
-    } else {
-        HIP_TRY(hipEventSynchronize(sn.ev));  // the slot's previous snapshot has landed (two posts ago)
-    }
-    // no flush: a pending (merged) M-step stays pending, so the snapshot holds the records of every
-    // iteration enqueued so far except the last one
-    hipLaunchKernelGGL(k_snapshot, dim3(1), dim3(256), 0, c->stream, c->state(), c->d_hist, (long long)first, sn.st,
-                       sn.hist);
-    HIP_TRY(hipGetLastError());
-    HIP_TRY(hipEventRecord(sn.ev, c->stream));
-    sn.first = first;
-    sn.ticket = c->snap_next++;
-    *ticket = sn.ticket;
-    return HMMBW_OK;
-}
-
-int hmmbw_status_wait(hmmbw_ctx *c, int64_t ticket, hmmbw_status *st, hmmbw_iter_record *rec, int64_t first,
-                      int64_t count) {
-    if (!c || !st) return fail(HMMBW_E_INVALID, "null argument");
-    if (ticket < 0 || ticket >= c->snap_next || ticket < c->snap_next - 2)
-        return fail(HMMBW_E_INVALID, "status ticket is not one of the last two posted");
-    if (int rc = set_device(c)) return rc;
-    hmmbw_ctx::Snap &sn = c->snaps[ticket % 2];
-    HIP_TRY(hipEventSynchronize(sn.ev));  // this snapshot only, not the work enqueued after it
-    const IterState h = *sn.st;
-    fill_status(h, st);
-    if (h.error) return fail(h.error, device_error(h));
-    if (rec && count > 0) {
-        if (first < sn.first || first + count > h.iteration || first + count > sn.first + kHist ||
-            first < h.iteration - kHist)  // overwritten in the ring before the snapshot was taken
-            return fail(HMMBW_E_INVALID, "requested iteration records are not in this snapshot");
-        for (int64_t i = 0; i < count; ++i) {
-            const int64_t k = first + i - sn.first;
-            rec[i].log_likelihood = sn.hist[2 * k];
-            rec[i].diff = sn.hist[2 * k + 1];
-        }
-    }
-    return HMMBW_OK;
-}
-
-int hmmbw_status_live_wait(hmmbw_ctx *c, int64_t iterations, hmmbw_status *st, hmmbw_iter_record *rec,
-                           int64_t first, int64_t count) {
-    if (!c || !st) return fail(HMMBW_E_INVALID, "null argument");
-    if (!c->h_live) return fail(HMMBW_E_STATE, "HMMBW_OPT_LIVE_STATUS is off");
-    if (int rc = set_device(c)) return rc;
-    volatile LiveBlock *lv = c->h_live;
-    IterState h{};
-    bool have = false;
-    for (long long spin = 0;; ++spin) {
-        const unsigned long long p0 = lv->pub;
-        std::atomic_thread_fence(std::memory_order_acquire);
-        if ((unsigned)(p0 >> 32) == c->live_epoch) {
-            const long long n = (long long)(unsigned)(p0 & 0xffffffffULL);
-            const volatile IterState &sl = lv->slot[n & 1];
-            h.prev_L = sl.prev_L;
-            h.last_L = sl.last_L;
-            h.last_diff = sl.last_diff;
-            h.epsilon = sl.epsilon;
-            h.iteration = sl.iteration;
-            h.max_iterations = sl.max_iterations;
-            h.done = sl.done;
-            h.converged = sl.converged;
-            h.error = sl.error;
-            std::atomic_thread_fence(std::memory_order_acquire);
-            const unsigned long long p1 = lv->pub;
-            // the slot is rewritten only by the record after next: two publications apart
-            const bool stable = (unsigned)(p1 >> 32) == c->live_epoch && (long long)(unsigned)(p1 & 0xffffffffULL) <= n + 1;
-            if (stable && h.iteration == n && (n >= iterations || h.done)) {
-                have = true;
-                break;
-            }
-        }
-        // the stream ran dry without the record (a pending M-step, a device-side stop the mirror does not
-        // carry, or a reset): the device state is the answer
-        if ((spin & 63) == 63 && hipStreamQuery(c->stream) == hipSuccess) {
-            const unsigned long long p2 = lv->pub;
-            if ((unsigned)(p2 >> 32) == c->live_epoch && (long long)(unsigned)(p2 & 0xffffffffULL) >= iterations) continue;
-            break;
-        }
-    }
-    std::vector<double> dh;
-    if (!have) {
-        HIP_TRY(hipMemcpy(&h, c->state(), sizeof(IterState), hipMemcpyDeviceToHost));
-        if (rec && count > 0) {
-            dh.resize(2 * (size_t)kHist);
-            HIP_TRY(hipMemcpy(dh.data(), c->d_hist, sizeof(double) * dh.size(), hipMemcpyDeviceToHost));
-        }
-    }
-    fill_status(h, st);
-    if (h.error) return fail(h.error, device_error(h));
-    if (rec && count > 0) {
-        if (first < 0 || first + count > h.iteration || first < h.iteration - kHist)
-            return fail(HMMBW_E_INVALID, "requested iteration records are not available");
-        for (int64_t i = 0; i < count; ++i) {
-            const int64_t k = (first + i) % kHist;
-            rec[i].log_likelihood = have ? lv->hist[2 * k] : dh[2 * k];
-            rec[i].diff = have ? lv->hist[2 * k + 1] : dh[2 * k + 1];
-        }
-    }
     return HMMBW_OK;
 }
 
@@ -1460,7 +931,7 @@ int hmmbw_score(hmmbw_ctx *c, double *out) {
     if (!out) return fail(HMMBW_E_INVALID, "null argument");
     if (int rc = check_closed(c)) return rc;
     if (int rc = flush_mstep(c)) return rc;
-    if (int rc = launch_estep(c, true, nullptr)) return rc;
+    if (int rc = launch_score(c)) return rc;
     return hmmbw_get_loglik(c, out);
 }
 

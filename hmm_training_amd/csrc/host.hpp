@@ -3,8 +3,10 @@
 // cross units.  Owners: alloc.hip (block cache, ledger), peer.hip (peer all-reduce), comm.hip (RCCL),
 // group.hip (grouped launches), viterbi.hip (hmmbw_viterbi and its kernels), posterior.hip (hmmbw_posterior and
 // its kernels), wordnet.hip (hmmbw_wordnet_decode and its kernels), embedded.hip (hmmbw_embedded_train and its
-// kernels; it keeps nothing in the context), align.hip (hmmbw_align and its kernels), hmmbw.hip (everything else,
-// and the definitions of the helpers below).  What wordnet.hip, embedded.hip and align.hip share beyond this
+// kernels; it keeps nothing in the context), align.hip (hmmbw_align and its kernels), train.hip (the M-step kernels
+// and the pending M-step, hmmbw_reset_training / _estep / _mstep / _iterate*), status.hip (the status readers, the
+// snapshot slots and the live mirror), hmmbw.hip (the life cycle, observations, options, parameters, the launch
+// planner, scoring and timing).  What wordnet.hip, embedded.hip and align.hip share beyond this
 // header, and the slot arguments they fill as viterbi.hip and posterior.hip do, is word_units.hpp's.
 // The observation layout and the launch map hmmbw.hip plans are obs_plan.hpp's: pure, shared with the
 // kernels, tested without a GPU (tests/test_obs_plan.py).
@@ -77,8 +79,20 @@ struct EventPairs {
     void destroy();
 };
 
-// One E-step / scorer launch of a context, resolved but not yet enqueued (launch_estep enqueues it
-// alone, group_launch concatenates several contexts' plans into one grouped launch).
+// Where one E-step launch reads and writes.  The three ways of filling it are hmmbw_ctx's io_local, io_packed and
+// io_fused, next to copies(e) / llpart(e).
+struct EstepIo {
+    const IterState *state = nullptr;  // the convergence state the launch reads (a done run is a no-op)
+    double *copies = nullptr;          // [ncopies][copy_len] statistics the launch adds into
+    double *llpart = nullptr;          // the per-workgroup (max, sum exp) pairs of log P it writes
+    double *zero = nullptr;            // zero_len doubles it clears for a later launch, or nullptr
+    long long zero_len = 0;
+    double *rank_ll = nullptr;         // fused all-reduce: this rank's pair, written by the last workgroup; or nullptr
+    int ncopies = 0;
+};
+
+// One E-step / scorer launch of a context, resolved but not yet enqueued (launch_estep / launch_score enqueue
+// it alone, group_launch concatenates several contexts' plans into one grouped launch).
 struct Plan {
     EArgs a{};
     KernelFn fn = nullptr;
@@ -298,6 +312,20 @@ struct hmmbw_ctx {
     IterState *state() const { return d_state + scur; }
     double *copies(long long e) const { return d_copies + (e % 3) * (long long)ncopies * copy_len(); }
     double *llpart(long long e) const { return d_llpart + (e % 2) * 2 * std::max(map.nblocks, 1LL); }
+    // E-step launch e of a single rank.  Statistics triple buffer: the launch adds into e, the merged M-step reads
+    // e - 1, and e + 1 (read by launch e - 2) is cleared for the next launch.
+    EstepIo io_local(long long e) const {
+        return EstepIo{state(), copies(e), llpart(e), copies(e + 1), (long long)ncopies * copy_len(), nullptr, ncopies};
+    }
+    // hmmbw_estep: one copy set, summed into the caller's packed statistics and cleared by k_reduce_local
+    EstepIo io_packed(long long e) const { return EstepIo{state(), copies(0), llpart(e), nullptr, 0, nullptr, ncopies}; }
+    // Fused all-reduce: the launch adds into buffer e of d_xbuf (the merged M-step reads the previous, all-reduced
+    // one), clears the next, and its last workgroup writes this rank's pair behind the xcopies() statistics copies.
+    EstepIo io_fused(long long e) const {
+        double *X = d_xbuf + (e % 3) * xlen, *Xn = d_xbuf + ((e + 1) % 3) * xlen;
+        const long long ll_off = (long long)xcopies() * copy_len();
+        return EstepIo{state(), X, llpart(e), Xn, xlen, X + ll_off + 2LL * rank, xcopies()};
+    }
 };
 
 namespace hmmbw {
@@ -308,16 +336,27 @@ void sync_ctx(hmmbw_ctx *c);
 long long ms_to_ticks(const hmmbw_ctx *c, long long ms);
 int check_ready(hmmbw_ctx *c, bool need_armed);
 int check_closed(const hmmbw_ctx *c);  // HMMBW_E_STATE between hmmbw_iterate_begin and _end
+int allow_lds(const void *f, size_t lds);
+// Resolve a training launch that reads and writes io; it runs the pending M-step in its prologue when that can
+// merge (which consumes c->pend).  allow_join: the joined spread map may serve it (a grouped launch cannot).
+int plan_estep(hmmbw_ctx *c, const EstepIo &io, bool allow_join, Plan *P);
+int plan_score(hmmbw_ctx *c, Plan *P);  // the forward-only scorer: log P of every sequence into d_logp
+int launch_estep(hmmbw_ctx *c, const EstepIo &io);
+int launch_score(hmmbw_ctx *c);
+int drain_timing(hmmbw_ctx *c);  // the queued E-step timing pairs into the context's sums
+
+// train.hip
+void init_state(hmmbw_ctx *c, IterState *slot, double epsilon, long long max_iterations);  // enqueues k_init_state
+MArgs make_margs(hmmbw_ctx *c, const hmmbw_ctx::Pending &p);
 int flush_mstep(hmmbw_ctx *c);
+// head of every training enqueue: the pending M-step runs now if the launch cannot merge it; *e: the launch's number
+int next_estep(hmmbw_ctx *c, long long *e);
 // the statistics of E-step launch e (nll log-likelihood pairs) become the pending M-step's input
 void pend_local(hmmbw_ctx *c, long long e, long long nll);
-int allow_lds(const void *f, size_t lds);
-int plan_estep(hmmbw_ctx *c, bool fwd_only, const IterState *state, double *copies, double *llpart, double *zero,
-               long long zero_len, bool merge, Plan *P, double *rank_ll = nullptr, int ncopies = 0,
-               bool allow_join = true);
-int launch_estep(hmmbw_ctx *c, bool fwd_only, const IterState *state, double *copies = nullptr,
-                 double *llpart = nullptr, double *zero = nullptr, long long zero_len = 0, bool merge = false,
-                 double *rank_ll = nullptr, int ncopies = 0);
+
+// status.hip
+int live_status_set(hmmbw_ctx *c, bool on);  // HMMBW_OPT_LIVE_STATUS: allocate and seed the host mirror, or free it
+void status_free(hmmbw_ctx *c);  // the snapshot slots and the live mirror; callers synchronise the device first
 
 // viterbi.hip
 void viterbi_free(hmmbw_ctx *c);  // the decoder's buffers; callers synchronise the context first

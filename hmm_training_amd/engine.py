@@ -359,12 +359,17 @@ class BaumWelchEngine:
     def reset(self, epsilon: float, max_iterations: int) -> None:
         check(self._lib.hmmbw_reset_training(self._ctx, float(epsilon), int(max_iterations)))
 
-    def status(self, first: int = 0, count: int = 0) -> Tuple[Status, List[Tuple[float, float]]]:
+    def _read_status(self, fn, head, first: int, count: int) -> Tuple[Status, List[Tuple[float, float]]]:
+        """Call a status-shaped entry point fn(ctx, *head, status, records, first, count): status + the records
+        [first, first + count)."""
         st = Status()
         recs = (IterRecord * max(count, 1))()
-        check(self._lib.hmmbw_get_status(self._ctx, ctypes.byref(st), ctypes.cast(recs, ctypes.c_void_p) if count
-                                         else None, int(first), int(count)))
+        check(fn(self._ctx, *head, ctypes.byref(st), ctypes.cast(recs, ctypes.c_void_p) if count > 0 else None,
+                 int(first), int(count)))
         return st, [(recs[i].log_likelihood, recs[i].diff) for i in range(count)]
+
+    def status(self, first: int = 0, count: int = 0) -> Tuple[Status, List[Tuple[float, float]]]:
+        return self._read_status(self._lib.hmmbw_get_status, (), first, count)
 
     def enqueue_iterations(self, n: int, stats: Optional[torch.Tensor] = None, group=None) -> None:
         """Enqueue n EM iterations (asynchronous).  Multi-rank when world_size > 1."""
@@ -423,6 +428,17 @@ class BaumWelchEngine:
         inflight = collections.deque()  # (ticket, iterations queued up to it)
         t_last = time.perf_counter()
         st = None
+
+        def report(recs, new):  # the callback and the metrics rows of the iterations [reported, reported + new)
+            nonlocal t_last
+            now = time.perf_counter()
+            if on_iteration is not None:
+                for k, (L, d) in enumerate(recs):
+                    on_iteration(reported + k, L, d)
+            if mfh is not None and new > 0:
+                self._write_metrics(mfh, reported, recs, now - t_last, new)
+            t_last = now
+
         try:
             while True:
                 if queued < max_it:
@@ -430,35 +446,21 @@ class BaumWelchEngine:
                     self.enqueue_iterations(n, stats, group)
                     queued += n
                     chunk = min(chunk * 2, max_chunk)
-                    tk = ctypes.c_int64()
-                    check(self._lib.hmmbw_status_post(self._ctx, reported, ctypes.byref(tk)))
-                    inflight.append((tk.value, queued))
+                    inflight.append((self.post_status(reported), queued))
                 if not inflight:
                     break
                 if len(inflight) < 2 and queued < max_it:
                     continue  # keep two snapshots' worth of work queued
                 ticket, upto = inflight.popleft()
                 st, recs = self._wait_status(ticket, reported)
-                now = time.perf_counter()
-                new = st.iterations - reported
-                if on_iteration is not None:
-                    for k, (L, d) in enumerate(recs):
-                        on_iteration(reported + k, L, d)
-                if mfh is not None and new > 0:
-                    self._write_metrics(mfh, reported, recs, now - t_last, new)
-                t_last = now
+                report(recs, st.iterations - reported)
                 reported = st.iterations
                 if st.done:
                     break
             st, recs = self.status(reported, 0)  # synchronous: flushes the pending M-step
             new = st.iterations - reported
             if new > 0:
-                recs = self.status(reported, new)[1]
-                if on_iteration is not None:
-                    for k, (L, d) in enumerate(recs):
-                        on_iteration(reported + k, L, d)
-                if mfh is not None:
-                    self._write_metrics(mfh, reported, recs, time.perf_counter() - t_last, new)
+                report(self.status(reported, new)[1], new)
         finally:
             if mfh is not None:
                 if timing_prev == 0:
@@ -482,12 +484,7 @@ class BaumWelchEngine:
                   count: int = 0) -> Tuple[Status, List[Tuple[float, float]]]:
         """Wait (polling the host mirror, no stream sync) until `iterations` EM iterations are recorded or EM
         stopped; status + the records [first, first+count)."""
-        st = Status()
-        recs = (IterRecord * max(count, 1))()
-        check(self._lib.hmmbw_status_live_wait(self._ctx, int(iterations), ctypes.byref(st),
-                                               ctypes.cast(recs, ctypes.c_void_p) if count else None,
-                                               int(first), int(count)))
-        return st, [(recs[i].log_likelihood, recs[i].diff) for i in range(count)]
+        return self._read_status(self._lib.hmmbw_status_live_wait, (int(iterations),), first, count)
 
     def wait_status(self, ticket: int, first: int = 0) -> Tuple[Status, List[Tuple[float, float]]]:
         """Wait for snapshot `ticket` only (not for the work queued after it): status + records [first, ...)."""
@@ -495,15 +492,11 @@ class BaumWelchEngine:
 
     def _wait_status(self, ticket: int, first: int) -> Tuple[Status, List[Tuple[float, float]]]:
         """Status snapshot `ticket` (hmmbw_status_wait) with the records of iterations [first, ...)."""
-        st = Status()
-        check(self._lib.hmmbw_status_wait(self._ctx, int(ticket), ctypes.byref(st), None, 0, 0))
+        st, _ = self._read_status(self._lib.hmmbw_status_wait, (int(ticket),), 0, 0)
         count = int(st.iterations) - int(first)
         if count <= 0:
             return st, []
-        recs = (IterRecord * count)()
-        check(self._lib.hmmbw_status_wait(self._ctx, int(ticket), ctypes.byref(st),
-                                          ctypes.cast(recs, ctypes.c_void_p), int(first), count))
-        return st, [(recs[i].log_likelihood, recs[i].diff) for i in range(count)]
+        return self._read_status(self._lib.hmmbw_status_wait, (int(ticket),), first, count)
 
     def _write_metrics(self, fh, first: int, recs, wall_s: float, enqueued: int) -> None:
         """One JSON line per iteration of the chunk: L and diff (hmm_training.py:503-514), the chunk's

@@ -112,3 +112,80 @@ def test_live_mirror_matches_sync_records_and_resets(merge):
         e.live_status(False)
         with pytest.raises(Exception):
             e.wait_live(1)
+
+
+# ---------------------------------------------------------------------------------------------
+# The record windows of the three readers (hmmbw_get_status, hmmbw_status_wait, hmmbw_status_live_wait): what each
+# refuses, with which code and text, and that all three return the same records of a ring that has wrapped.
+# ---------------------------------------------------------------------------------------------
+K_HIST = 4096          # kHist (hmmbw_args.hpp): iteration i's record lies at i % kHist
+WRAP_ITERS = 4200      # 104 records overwritten
+OLDEST = WRAP_ITERS - K_HIST
+NOT_AVAILABLE = "requested iteration records are not available"
+NOT_IN_SNAPSHOT = "requested iteration records are not in this snapshot"
+READERS = {"get": NOT_AVAILABLE, "wait": NOT_IN_SNAPSHOT, "live": NOT_AVAILABLE}
+
+
+@pytest.fixture(scope="module")
+def wrapped():
+    """An engine after 4,200 iterations (N = 2, K = 4, four sequences of T = 3, epsilon = 0) with the live mirror
+    on, and two snapshots of the finished run: one posted from iteration 0, one from the oldest record the ring
+    still holds."""
+    from hmm_training_amd.engine import BaumWelchEngine
+    from hmm_training_amd.hmm_training import default_initial_params
+    rng = np.random.default_rng(3)
+    e = BaumWelchEngine(2, 4, topology="left_to_right")
+    e.set_observations([rng.integers(0, 4, size=3) for _ in range(4)])
+    e.set_params(*default_initial_params(2, 4))
+    e.live_status(True)
+    e.reset(0.0, WRAP_ITERS)
+    e.enqueue_iterations(WRAP_ITERS)
+    st, _ = e.status()  # flushes the last M-step: the snapshots and the mirror hold the whole run
+    assert st.iterations == WRAP_ITERS and st.done
+    tickets = {0: e.post_status(0), OLDEST: e.post_status(OLDEST)}
+    yield e, tickets
+    e.close()
+
+
+def read_raw(e, tickets, reader, first, count, posted_from=0):
+    """(code, error text, records) of one reader's raw call for the records [first, first + count)."""
+    from hmm_training_amd._lib import IterRecord, Status
+    st = Status()
+    recs = (IterRecord * max(count, 1))()
+    tail = (ctypes.byref(st), ctypes.cast(recs, ctypes.c_void_p), first, count)
+    if reader == "get":
+        rc = e._lib.hmmbw_get_status(e._ctx, *tail)
+    elif reader == "wait":
+        rc = e._lib.hmmbw_status_wait(e._ctx, tickets[posted_from], *tail)
+    else:
+        rc = e._lib.hmmbw_status_live_wait(e._ctx, WRAP_ITERS, *tail)
+    msg = e._lib.hmmbw_last_error().decode() if rc else ""
+    assert st.iterations == WRAP_ITERS and st.done  # the status is filled before the window is looked at
+    return rc, msg, [(recs[i].log_likelihood, recs[i].diff) for i in range(count if rc == 0 else 0)]
+
+
+@pytest.mark.parametrize("reader", list(READERS))
+@pytest.mark.parametrize("first,count,why", [(-1, 1, "first < 0"), (WRAP_ITERS - 1, 2, "past the last iteration"),
+                                             (OLDEST - 1, 1, "overwritten in the ring")])
+def test_record_window_refusals_keep_their_code_and_text(wrapped, reader, first, count, why):
+    from hmm_training_amd._lib import HMMBW_E_INVALID
+    e, tickets = wrapped
+    rc, msg, _ = read_raw(e, tickets, reader, first, count)
+    assert (rc, msg) == (HMMBW_E_INVALID, READERS[reader]), why
+
+
+def test_last_ring_of_records_is_equal_across_the_readers(wrapped):
+    e, tickets = wrapped
+    got = {}
+    for reader in READERS:
+        rc, msg, recs = read_raw(e, tickets, reader, OLDEST, K_HIST, posted_from=OLDEST)
+        assert rc == 0, f"{reader}: {msg}"
+        got[reader] = recs
+    assert len(got["get"]) == K_HIST and np.all(np.isfinite(got["get"]))
+    assert got["wait"] == got["get"] and got["live"] == got["get"]
+    # a ring that wrapped is read in iteration order: each record's diff is |L - L of the record before| (mstep.hpp,
+    # record_iteration), the same fp64 subtraction here
+    L, diff = np.array(got["get"]).T
+    assert np.array_equal(diff[1:], np.abs(L[1:] - L[:-1]))
+    # the snapshot posted from iteration 0 holds the ring's slots in slot order, so it cannot serve this window
+    assert read_raw(e, tickets, "wait", OLDEST, K_HIST)[1] == NOT_IN_SNAPSHOT

@@ -26,6 +26,12 @@ def test_library_exports_every_header_symbol():
     assert lib.hmmbw_abi_version() == _lib.ABI_VERSION == 5
 
 
+@pytest.mark.parametrize("name", ["train.hip", "status.hip"])
+def test_build_compiles_the_training_and_status_units(name):
+    from hmm_training_amd import build
+    assert any(os.path.basename(src) == name for src, _, _ in build.units())
+
+
 def test_library_fails_loudly_without_device_or_bad_args():
     from hmm_training_amd import _lib
     lib = _lib.lib()

@@ -9,7 +9,9 @@ library.  From every object of both sides the gfx950 code object is unbundled (l
 --dump-section=.hip_fatbin, clang-offload-bundler --unbundle) and disassembled (llvm-objdump -d).  Compared per
 kernel: the instruction text (operands and branch offsets included, addresses and encodings dropped) and, from the
 code object's notes (llvm-readelf --notes), the agpr / vgpr / sgpr counts, the group (LDS) and private (scratch)
-segment sizes and the spill counts.  Then the exported hmmbw_ symbols of the two libraries (the objects linked as
+segment sizes and the spill counts.  A kernel is paired with the one of its name in the same unit; one that a unit
+has on one side only (it moved to another unit, or its unit is new) is paired by name across the units.  Then the
+exported hmmbw_ symbols of the two libraries (the objects linked as
 build() links them, unless --libs names them).  Prints one line per translation unit, the differing kernels
 under it, and exits 1 on any difference.  The text is only compared and hashed; what the instructions are is
 not looked at.  profiles/r8/isa_identity.txt and profiles/r9/isa_identity.txt are this table.
@@ -70,6 +72,11 @@ def streams(co: str) -> dict:
             cur = out.setdefault(m.group(1), [])
         elif cur is not None and line[:1] in " \t" and line.strip():
             cur.append(line.split("//", 1)[0].strip())
+    # the fill between a symbol's last instruction and the next symbol's alignment (the end of the code object
+    # after the last one) depends on what follows it in the unit, not on the kernel
+    for v in out.values():
+        while v and v[-1] in ("s_nop 0", "s_code_end"):
+            v.pop()
     return out
 
 
@@ -165,25 +172,42 @@ def main() -> int:
             res = list(ex.map(lambda j: unit(*j) if os.path.exists(j[0]) else None, jobs))
         print("# per translation unit: kernels, instructions, sha256 of all instruction text (parent == new?), "
               "resource figures equal?")
+        # symbols a unit has on one side only (a kernel that moved unit, a unit that is new): paired by name below
+        lost, found = {}, {}
         for i, s in enumerate(stems):
-            a, b = res[2 * i], res[2 * i + 1]
-            if a is None or b is None:
-                same = False
-                print(f"{s:<18} only in {'new' if a is None else 'parent'}")
+            (sa, fa), (sb, fb) = res[2 * i] or ({}, {}), res[2 * i + 1] or ({}, {})
+            lost.update({k: (s, sa[k], fa.get(k)) for k in sa if k not in sb})
+            found.update({k: (s, sb[k], fb.get(k)) for k in sb if k not in sa})
+            if res[2 * i] is None or res[2 * i + 1] is None:
+                print(f"{s:<18} only in {'new' if res[2 * i] is None else 'parent'}: {len(sa) + len(sb)} symbols, by name below")
                 continue
-            (sa, fa), (sb, fb) = a, b
-            text = [sha([f"{k}:"] + v) for k, v in sorted(sa.items())], [sha([f"{k}:"] + v) for k, v in sorted(sb.items())]
-            ok_s, ok_f = sa == sb, fa == fb
+            both = sorted(set(sa) & set(sb))
+            text = [sha([f"{k}:"] + sa[k]) for k in both], [sha([f"{k}:"] + sb[k]) for k in both]
+            ok_s = all(sa[k] == sb[k] for k in both)
+            ok_f = all(fa.get(k) == fb.get(k) for k in both)
             same = same and ok_s and ok_f
-            print(f"{s:<18} kernels {len(fa):4d} instructions {sum(len(v) for v in sa.values()):9d} "
+            moved = f" ({len(sa) - len(both)} left, {len(sb) - len(both)} joined: by name below)" if len(sa) != len(both) or len(sb) != len(both) else ""
+            print(f"{s:<18} kernels {sum(k in fa for k in both):4d} instructions {sum(len(sa[k]) for k in both):9d} "
                   f"sha {sha(text[0])} / {sha(text[1])} streams {'identical' if ok_s else 'DIFFER'} "
-                  f"figures {'identical' if ok_f else 'DIFFER'}")
-            for k in sorted(set(sa) | set(sb)):
-                if sa.get(k) != sb.get(k) or fa.get(k) != fb.get(k):
-                    na, nb = len(sa.get(k, ())), len(sb.get(k, ()))
-                    moved = f" ({sum(x != y for x, y in zip(sa[k], sb[k]))} lines differ in place)" if na == nb else ""
-                    print(f"    {k}: instructions {na} -> {nb}{moved}"
+                  f"figures {'identical' if ok_f else 'DIFFER'}{moved}")
+            for k in both:
+                if sa[k] != sb[k] or fa.get(k) != fb.get(k):
+                    na, nb = len(sa[k]), len(sb[k])
+                    inplace = f" ({sum(x != y for x, y in zip(sa[k], sb[k]))} lines differ in place)" if na == nb else ""
+                    print(f"    {k}: instructions {na} -> {nb}{inplace}"
                           + ("" if fa.get(k) == fb.get(k) else f"; {', '.join(FIGURES)}: {fa.get(k)} -> {fb.get(k)}"))
+        if lost or found:
+            print("# symbols whose unit changed, paired by name: parent unit -> new unit")
+        for k in sorted(set(lost) | set(found)):
+            if k not in lost or k not in found:
+                same = False
+                print(f"    {k}: only in {'parent ' + lost[k][0] if k in lost else 'new ' + found[k][0]}")
+                continue
+            (ua, xa, ga), (ub, xb, gb) = lost[k], found[k]
+            ok_s, ok_f = xa == xb, ga == gb
+            same = same and ok_s and ok_f
+            print(f"    {k}: {ua} -> {ub} instructions {len(xa)} -> {len(xb)} streams {'identical' if ok_s else 'DIFFER'} "
+                  f"figures {'identical' if ok_f else 'DIFFER'}" + ("" if ok_f else f"; {', '.join(FIGURES)}: {ga} -> {gb}"))
         libs = args.libs or [lib or link(d, os.path.join(tmp, f"libhmmbw_{side}.so"))
                              for side, (d, lib) in zip(("parent", "new"), sides)]
         ea, eb = exported(libs[0]), exported(libs[1])
