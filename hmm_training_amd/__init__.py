@@ -10,7 +10,8 @@ __all__ = ["HMMTrained", "DataStorageHMM", "hmm_training", "training_with_save",
            "BaumWelchEngine",
            "lbg_train",
            "createCodeVector", "save_centroids", "train_connected", "frame_table", "mfcc_frames", "mfcc_recordings",
-           "encode_recordings", "with_optional"]
+           "encode_recordings", "with_optional", "read_wav", "preprocess_recordings", "encode_raw_recordings",
+           "recognise_recordings"]
 
 
 def __getattr__(name):
@@ -26,9 +27,16 @@ def __getattr__(name):
     if name in ("lbg_train", "createCodeVector", "LBGResult"):
         from . import codevector as _cv
         return getattr(_cv, name)
-    if name in ("frame_table", "mfcc_frames", "mfcc_recordings", "encode_recordings"):
+    if name in ("frame_table", "mfcc_frames", "mfcc_recordings", "encode_recordings", "preprocess_recordings",
+                "encode_raw_recordings"):
         from . import frontend as _fe
         return getattr(_fe, name)
+    if name == "recognise_recordings":
+        from .hmm_testing import recognise_recordings
+        return recognise_recordings
+    if name == "read_wav":
+        from .io import read_wav
+        return read_wav
     if name == "save_centroids":
         from .io import save_centroids
         return save_centroids

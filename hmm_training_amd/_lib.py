@@ -42,6 +42,7 @@ EXPORTED = (
     "hmmbw_peer_attach", "hmmbw_allreduce_kind", "hmmbw_status_live_wait", "hmmbw_get_option", "hmmbw_viterbi",
     "hmmbw_posterior", "hmmbw_lbg_train", "hmmbw_wordnet_decode", "hmmbw_embedded_train",
     "hmmbw_mfcc", "hmmbw_mfcc_tables", "hmmbw_align", "hmmbw_align_optional", "hmmbw_embedded_train_optional",
+    "hmmbw_preprocess", "hmmbw_window_overlap",
 )
 ABI_VERSION = 5
 OPT_SAFE_SCALING = 1
@@ -72,6 +73,8 @@ EMBED_END_FINAL = 1
 EMBED_DENSE = 2
 ALIGN_END_FINAL = 1
 ALIGN_DENSE = 2
+SAMPLES_F64 = 0
+SAMPLES_I16 = 1
 
 
 class HMMBWError(RuntimeError):
@@ -174,6 +177,11 @@ def _declare(lib):
                                       ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int,
                                       ctypes.c_void_p, ctypes.c_int, ctypes.c_double, ctypes.c_double, ctypes.c_void_p,
                                       ctypes.c_int64]),
+        "hmmbw_preprocess": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p,
+                                            ctypes.c_void_p, ctypes.c_int64, ctypes.c_double, ctypes.c_int, ctypes.c_int,
+                                            ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]),
+        "hmmbw_window_overlap": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
+                                                ctypes.c_int64, ctypes.c_void_p, ctypes.c_int, ctypes.c_int]),
         "hmmbw_comm_probe": (ctypes.c_int, [ctypes.c_char_p]),
         "hmmbw_comm_unique_id": (ctypes.c_int, [ctypes.c_char_p, ctypes.c_void_p]),
         "hmmbw_comm_init": (ctypes.c_int, [c_ctx, ctypes.c_char_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_int,

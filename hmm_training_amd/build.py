@@ -6,7 +6,8 @@ scoring; train.hip: the M-step kernels and the training ABI; status.hip: the sta
 group.hip: grouped launches; viterbi.hip: the Viterbi decoder and its kernels; posterior.hip: the state
 posteriors and their kernels; lbg.hip: LBG codebook training and its kernels; wordnet.hip: connected-word
 decoding and its kernels; embedded.hip: embedded training over transcribed word sequences and its kernels;
-mfcc.hip: the MFCC front end and its kernel; align.hip: forced alignment to a transcript and its kernels; what
+mfcc.hip: the MFCC front end and its kernel; preproc.hip: signal conditioning (filter, trim, overlapping window) and
+its kernels, built with -ffp-contract=off; align.hip: forced alignment to a transcript and its kernels; what
 wordnet.hip, embedded.hip and align.hip share is csrc/word_units.hpp, a header and no unit of its own), the VQ
 encoder (csrc/vq.hip), one small-N E-step instantiation unit per
 state count N = 1..16 (csrc/estep_small_inst.hip with -DHMMBW_INST_N=n) and the wide-N unit
@@ -44,7 +45,9 @@ def units():
     u += [(os.path.join(CSRC, s + ".hip"), [], s) for s in ("train", "status", "alloc", "peer", "comm", "group", "viterbi",
                                                             "posterior", "lbg", "wordnet", "embedded", "mfcc",
                                                             "align")]
-    u += [(os.path.join(CSRC, "estep_small_inst.hip"), [f"-DHMMBW_INST_N={n}"], f"estep_small_n{n}")
+    # signal conditioning reproduces the reference's filter bit for bit: no product is fused into an addition
+    u += [(os.path.join(CSRC, "preproc.hip"), ["-ffp-contract=off"], "preproc")]
+    u +=[(os.path.join(CSRC, "estep_small_inst.hip"), [f"-DHMMBW_INST_N={n}"], f"estep_small_n{n}")
           for n in SMALL_N]
     return u
 

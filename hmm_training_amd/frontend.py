@@ -10,6 +10,12 @@ of recordings in one launch per distinct frame length, the rows left on the devi
 * ``mfcc_frames``: RawDataMFCC.calculate_mfcc for each frame of a list;
 * ``mfcc_recordings``: signals in, one [T_r, n_mfcc] array per signal out;
 * ``encode_recordings``: signals in, observation symbols out (process_recording + get_observations).
+
+In front of it, signal conditioning (``hmmbw_preprocess``, ``hmmbw_window_overlap``): the reference's preemphasis.py
+and the do_preemphasis of its live recogniser, raw recording -> processed signal:
+
+* ``preprocess_recordings``: raw recordings in, trimmed (and windowed) signals and their bounds out;
+* ``encode_raw_recordings``: raw recordings in, observation symbols out, nothing on the host in between.
 """
 from __future__ import annotations
 
@@ -21,6 +27,10 @@ import numpy as np
 AMIN = 1e-10    # librosa.power_to_db's defaults, which librosa.feature.mfcc uses
 TOP_DB = 80.0
 MIN_TAIL = 12   # a remainder frame needs more samples than this (:428)
+PREEMPHASIS = 0.95                      # filter_signal, preemphasis.py:179
+FACTORS = {"batch": (-1.0, 0.015, -1.0, 0.015),   # (zf, pf, zl, pl): slice_signal of preemphasis.py:256 (no zcr test)
+           "live": (0.08, 0.15, 0.03, 0.10)}      # ... and of HMM/live_testing.py:80-88
+WINDOW_LEN, WINDOW_HOP = 320, 128       # hamming_window, preemphasis.py:190-191
 
 _tables: Dict[tuple, tuple] = {}  # (L, sample_rate, n_mels, n_mfcc, device) -> (window, twiddle, mel, dct) on the device
 
@@ -164,6 +174,153 @@ def mfcc_recordings(signals: Sequence, sample_rate: int = 16000, n_mfcc: int = 1
         rows = out.cpu().numpy()
     pos = np.concatenate([[0], np.cumsum(counts)]).astype(np.int64)
     return [rows[pos[i]:pos[i + 1]].copy() for i in range(len(counts))]
+
+
+def _raw_signal(x) -> np.ndarray:
+    """Column 0 of a 2-D recording (the reference reads signal[i, 0]); int16 stays int16, the rest becomes float64."""
+    a = np.asarray(x)
+    if a.ndim == 2:
+        a = a[:, 0]
+    elif a.ndim != 1:
+        raise ValueError("a recording is a 1-D array or an (n, channels) array")
+    return np.ascontiguousarray(a if a.dtype == np.int16 else a.astype(np.float64))
+
+
+def hamming_table(wlen: int = WINDOW_LEN) -> np.ndarray:
+    """The reference's window table (preemphasis.py:194-195), built with NumPy as it builds it."""
+    return 0.54 - 0.46 * np.cos((2 * np.pi * np.arange(wlen)) / (wlen - 1))
+
+
+def _conditioned_on_device(signals: Sequence, sample_rate, mode, factors, window, dev, want_stats=False):
+    """Enqueue hmmbw_preprocess (and hmmbw_window_overlap) on the current stream.  Returns (y [N] on the device,
+    bounds [R, 2] on the device, offsets (host, int64 [R + 1]), stats [sum nf, 2] on the device or None)."""
+    import torch
+
+    from ._lib import SAMPLES_F64, SAMPLES_I16, check, lib
+    if mode not in FACTORS:
+        raise ValueError("mode is 'batch' or 'live'")
+    fac = np.ascontiguousarray(FACTORS[mode] if factors is None else factors, dtype=np.float64)
+    if fac.shape != (4,):
+        raise ValueError("factors are (zf, pf, zl, pl)")
+    if window is None:
+        window = mode == "live"
+    sigs = [_raw_signal(s) for s in signals]
+    as_i16 = all(s.dtype == np.int16 for s in sigs)
+    if not as_i16:
+        sigs = [s.astype(np.float64) for s in sigs]
+    offs = np.concatenate([[0], np.cumsum([len(s) for s in sigs])]).astype(np.int64)
+    win, hop = int(0.02 * sample_rate), int(0.01 * sample_rate)
+    R = len(sigs)
+    p = lambda t: ctypes.c_void_p(t.data_ptr())  # noqa: E731
+    stream = ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+    tx = torch.from_numpy(np.concatenate(sigs) if R else np.zeros(0)).to(dev)
+    toff = torch.from_numpy(offs).to(dev)
+    y = torch.empty(int(offs[-1]), dtype=torch.float64, device=dev)
+    bounds = torch.zeros((R, 2), dtype=torch.int64, device=dev)
+    stats = None
+    if want_stats:
+        nf = sum(max(int((len(s) - win) / hop) + 1, 0) for s in sigs) if hop > 0 else 0
+        stats = torch.zeros((nf, 2), dtype=torch.float64, device=dev)
+    L_ = lib()
+    if R == 0:
+        return y, bounds, offs, stats
+    check(L_.hmmbw_preprocess(stream, p(tx), SAMPLES_I16 if as_i16 else SAMPLES_F64, p(toff),
+                              ctypes.c_void_p(offs.ctypes.data), R, PREEMPHASIS, win, hop,
+                              ctypes.c_void_p(fac.ctypes.data), p(y), p(bounds), p(stats) if want_stats else None))
+    if window is not False and window is not None:
+        table = hamming_table() if window is True else np.ascontiguousarray(window, dtype=np.float64).reshape(-1)
+        tw = torch.from_numpy(table).to(dev)
+        check(L_.hmmbw_window_overlap(stream, p(y), p(toff), p(bounds), R, p(tw), len(table), WINDOW_HOP))
+    return y, bounds, offs, stats
+
+
+def preprocess_recordings(signals: Sequence, sample_rate: int = 16000, mode: str = "batch", factors=None, window=None,
+                          device: Optional[int] = None, return_stats: bool = False):
+    """(trimmed, bounds): the reference's signal conditioning of every raw recording, on the GPU (hmmbw_preprocess):
+    the filter 1 - 0.95 z^-1, the power / zero-crossing trim, and in live mode the overlapping Hamming window.
+
+    ``signals``: 1-D arrays or (n, channels) arrays (column 0 is taken, as the reference does); int16 recordings go
+    up as int16.  ``mode``: "batch" is preemphasis.py (what it ``np.save``s under Data/Processed), "live" is
+    HMM/live_testing.do_preemphasis; ``factors`` (zf, pf, zl, pl) overrides the mode's thresholds; ``window`` is
+    False (off, batch default), True (the 320-sample Hamming table at hop 128, live default) or a table of its own.
+    ``trimmed`` is a list of (m, 1) float64 arrays, ``bounds`` int64 [R, 2] (start, finish) within each recording.
+    With ``return_stats`` a third value: one [nf, 2] array (zcr, power) per recording.
+    A recording too short for one 20 ms frame raises ValueError, as the reference raises.  All arithmetic is fp64: for
+    int16 and float64 recordings the result is the reference's bit for bit; the float32 arithmetic NumPy 2 gives the
+    reference's filter for a float32 recording is not reproduced."""
+    import torch
+    dev = _device(device)
+    with torch.cuda.device(dev):
+        y, bounds, offs, stats = _conditioned_on_device(signals, sample_rate, mode, factors, window, dev, return_stats)
+        yh, bh = y.cpu().numpy(), bounds.cpu().numpy()
+        sh = stats.cpu().numpy() if return_stats else None
+    trimmed = [yh[o + b[0]:o + b[1]].reshape(-1, 1).copy() for o, b in zip(offs[:-1], bh)]
+    if not return_stats:
+        return trimmed, bh
+    win, hop = int(0.02 * sample_rate), int(0.01 * sample_rate)
+    nf = [int((int(n) - win) / hop) + 1 for n in np.diff(offs)]
+    pos = np.concatenate([[0], np.cumsum(nf)]).astype(np.int64)
+    return trimmed, bh, [sh[pos[i]:pos[i + 1]].copy() for i in range(len(nf))]
+
+
+def _codebook_array(centroids) -> np.ndarray:
+    if isinstance(centroids, np.ndarray):
+        return np.ascontiguousarray(centroids, dtype=np.float64)
+    if len(centroids) == 0:
+        return np.zeros((0, 13))
+    return np.stack([np.asarray(c.mfcc, dtype=np.float64).reshape(-1) for c in centroids])
+
+
+def encode_raw_recordings(signals: Sequence, centroids, mode: str = "batch", sample_rate: int = 16000, factors=None,
+                          window=None, n_mels: int = 26, frame_size: int = 320, hop_size: int = 160,
+                          device: Optional[int] = None) -> List[np.ndarray]:
+    """Observation symbols of every RAW recording: hmmbw_preprocess (and the window in live mode), hmmbw_mfcc and
+    hmmbw_vq_encode on one stream; the conditioned signal and the MFCC rows never leave the device.  The frames of
+    recording r are ``frame_table(m_r)`` from its trimmed start.  One small read-back (the bounds, [R, 2]) sits
+    between the stages: the frame count is a host argument of hmmbw_mfcc.  Returns what ``encode_recordings`` returns
+    for the conditioned signals: an int64 array per recording (an empty array where nothing is left)."""
+    import torch
+
+    from ._lib import check, lib
+    C = _codebook_array(centroids)
+    K, D = C.shape
+    if K > 0:
+        _check_settings(D, n_mels)
+    dev = _device(device)
+    with torch.cuda.device(dev):
+        y, bounds, offs, _ = _conditioned_on_device(signals, sample_rate, mode, factors, window, dev)
+        bh = bounds.cpu().numpy()  # the one read-back
+        starts, lengths, counts = [], [], []
+        for o, (b0, b1) in zip(offs[:-1], bh):
+            st, ln = frame_table(max(int(b1 - b0), 0), frame_size, hop_size)
+            starts.append(st + int(o) + int(b0))
+            lengths.append(ln)
+            counts.append(len(st))
+        starts = np.concatenate(starts) if starts else np.zeros(0, np.int64)
+        lengths = np.concatenate(lengths) if lengths else np.zeros(0, np.int64)
+        if K == 0:  # get_observations with an empty codebook
+            return [np.zeros(T, dtype=np.int64) for T in counts]
+        F = len(starts)
+        if F == 0:
+            return [np.array([]) for _ in counts]
+        if lengths.min() < 2:
+            raise ValueError("a frame needs at least 2 samples")
+        rows = torch.empty((F, D), dtype=torch.float64, device=dev)
+        _run(y, starts, lengths, rows, dev, sample_rate, D, n_mels, AMIN, TOP_DB)
+        if D < 2:
+            sym = np.zeros(F, dtype=np.int64)
+        else:
+            tc = torch.from_numpy(C).to(dev)
+            ts = torch.empty(F, dtype=torch.int32, device=dev)
+            stream = torch.cuda.current_stream(dev).cuda_stream
+            check(lib().hmmbw_vq_encode(ctypes.c_void_p(stream), ctypes.c_void_p(rows.data_ptr()), F, D, 1, D - 1,
+                                        ctypes.c_void_p(tc.data_ptr()), K, ctypes.c_void_p(ts.data_ptr()), None))
+            sym = ts.cpu().numpy().astype(np.int64)
+    out, pos = [], 0
+    for T in counts:
+        out.append(sym[pos:pos + T] if T else np.array([]))
+        pos += T
+    return out
 
 
 def encode_recordings(signals: Sequence, centroids, sample_rate: int = 16000, n_mels: int = 26, frame_size: int = 320,

@@ -160,6 +160,25 @@ def align_words(observations: Sequence[np.ndarray], transcripts: Sequence[Sequen
     return segments, logp
 
 
+def recognise_recordings(signals: Sequence, models: Sequence[HMMTrained], centroids, mode: str = "live",
+                         sample_rate: int = 16000, device=None) -> Tuple[np.ndarray, List[list]]:
+    """(scores [R, W], ranking): HMM/live_testing.main from do_preemphasis to the sorted dictionary, without the
+    microphone and for any number of recordings: raw recording -> conditioning -> frames -> MFCC -> symbols
+    (frontend.encode_raw_recordings) -> log P(O | model) of every model (score_matrix, one launch).  ranking[r] lists
+    the models' .word names by descending score; ties keep the models' order, as Python's stable sort keeps the
+    dictionary's.  A recording that trims to no frame has no observation: its row is -inf throughout and it takes no
+    part in the scoring launch."""
+    from .frontend import encode_raw_recordings
+    obs = encode_raw_recordings(signals, centroids, mode=mode, sample_rate=sample_rate, device=device)
+    scores = np.full((len(obs), len(models)), -np.inf)
+    live = [r for r, o in enumerate(obs) if len(o) > 0]
+    if live and len(models):
+        scores[live] = score_matrix([obs[r] for r in live], models, device=device)
+    words = [h.word for h in models]
+    ranking = [[words[m] for m in sorted(range(len(words)), key=lambda m: row[m], reverse=True)] for row in scores]
+    return scores, ranking
+
+
 def calculate_log_likelihood(recording_observations: np.ndarray, hmm: HMMTrained) -> float:
     """log P(O | lambda) of one sequence under one linear-domain model (hmm_testing.py:49-104)."""
     return float(score_matrix([np.asarray(recording_observations)], [hmm])[0, 0])

@@ -47,6 +47,18 @@ def save_centroids(path: str, centroids) -> None:
         json.dump(data, fh, indent=2)
 
 
+def read_wav(path: str):
+    """(samples int16 [n, channels], framerate) of a 16-bit PCM .wav file, with the standard library's ``wave`` as
+    the reference's open_file / assing_step_time read it (preemphasis.py:127-170)."""
+    import wave
+    with wave.open(str(path), "rb") as w:
+        if w.getsampwidth() != 2:
+            raise ValueError(f"{path}: {8 * w.getsampwidth()}-bit samples; 16-bit PCM is what the reference reads")
+        channels, rate = w.getnchannels(), w.getframerate()
+        raw = w.readframes(w.getnframes())
+    return np.frombuffer(raw, dtype="<i2").astype(np.int16).reshape(-1, channels), rate
+
+
 def load_frames(path: str, recompute_mfcc: bool = False) -> List[Frame]:
     """The frames of a ``*_frames.json``.  ``recompute_mfcc``: every frame's MFCC is computed from its ``raw_samples``
     at its ``sample_rate`` (RawDataMFCC.__post_init__, :217-224; a frame without samples keeps its stored vector)."""

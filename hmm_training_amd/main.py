@@ -7,6 +7,8 @@ reference's CodeVector pipeline).
     python -m hmm_training_amd.main codebook --frames PATH [PATH ...] --out codevector.json
                                              [--centroids 256 --max-iterations 100 --epsilon 0.001]
     python -m hmm_training_amd.main features --signals PATH.npy [PATH.npy ...] --out-dir DIR
+    python -m hmm_training_amd.main preprocess --wav PATH.wav [PATH.wav ...] --out-dir DIR
+    python -m hmm_training_amd.main recognise --wav PATH.wav [PATH.wav ...] [--models DIR] [--data ../Data]
 
 Same on-disk layout as the reference:
 * ``<data>/CodeVector/codevector.json`` — the codebook;
@@ -238,9 +240,72 @@ def features(signal_paths: List[str], out_dir: str, sample_rate: int = 16000) ->
     return written
 
 
+def _read_16k(wav_paths: List[str], sample_rate: int = 16000):
+    """The int16 samples of every file, or None (with a message) when one is not at ``sample_rate``: the reference
+    resamples such a file in place (check_metadata), which is out of scope here."""
+    from .io import read_wav
+    signals = []
+    for path in wav_paths:
+        samples, rate = read_wav(path)
+        if rate != sample_rate:
+            print(f"{path}: sample rate {rate} Hz, not {sample_rate} Hz; resample it first (not done here)")
+            return None
+        signals.append(samples)
+    return signals
+
+
+def preprocess(wav_paths: List[str], out_dir: str, sample_rate: int = 16000) -> Optional[List[str]]:
+    """The reference's preemphasis.py on the GPU: filter and trim every ``.wav`` recording and write
+    ``<out_dir>/<stem>.npy``, the (m, 1) float64 array the reference saves under Data/Processed, which ``features``
+    reads.  None when a file is refused."""
+    import numpy as np
+
+    from .frontend import preprocess_recordings
+    signals = _read_16k(wav_paths, sample_rate)
+    if signals is None:
+        return None
+    trimmed, bounds = preprocess_recordings(signals, sample_rate=sample_rate, mode="batch")
+    os.makedirs(out_dir, exist_ok=True)
+    written = []
+    for path, t, b in zip(wav_paths, trimmed, bounds):
+        out = os.path.join(out_dir, f"{Path(path).stem}.npy")
+        np.save(out, t)
+        print(f"    Saved samples [{int(b[0])}, {int(b[1])}) of {path} to {out}")
+        written.append(out)
+    return written
+
+
+def recognise(wav_paths: List[str], base_dir="../Data", model_dir: Optional[str] = None, sample_rate: int = 16000):
+    """HMM/live_testing.main for recordings on disk: live-mode conditioning, symbols, every model's log-likelihood, and
+    its two printed lines per recording.  Returns (scores, ranking) or None."""
+    from .hmm_testing import recognise_recordings
+    all_hmm = DataStorageHMM.load_all_hmms(base_dir=model_dir) if model_dir else DataStorageHMM.load_all_hmms()
+    if not all_hmm:
+        print("No trained HMM models found. Please train models first.")
+        return None
+    centroids = load_mfcc_centroids(base_dir, print_messages=False)
+    signals = _read_16k(wav_paths, sample_rate)
+    if signals is None:
+        return None
+    scores, ranking = recognise_recordings(signals, all_hmm, centroids, mode="live", sample_rate=sample_rate)
+    words = [h.word for h in all_hmm]
+    for path, row, order in zip(wav_paths, scores, ranking):
+        if len(wav_paths) > 1:
+            print(path)
+        by_word = dict(zip(words, row))
+        print("Likelihoods ")
+        print(" ".join(f"{w}: {float(by_word[w]):.3f}" for w in words), end=" ")
+        print("\n")
+        print("Sorted: ")
+        print(" ".join(f"{w}: {float(by_word[w]):.3f}" for w in order), end=" ")
+        print("\n")
+    return scores, ranking
+
+
 def _cli(argv=None):
     ap = argparse.ArgumentParser(description=__doc__.splitlines()[0])
-    ap.add_argument("command", choices=["train", "test", "codebook", "features"])
+    ap.add_argument("command", choices=["train", "test", "codebook", "features", "preprocess", "recognise"])
+    ap.add_argument("--wav", nargs="+", default=None, help="preprocess, recognise: raw 16 kHz recordings (.wav)")
     ap.add_argument("--data", default="../Data")
     ap.add_argument("--models", default=None, help="model directory (default: DataStorageHMM's)")
     # `python main.py train` runs train_hmm(show_progress=True, max_iterations=2) (HMM/main.py:268);
@@ -261,6 +326,14 @@ def _cli(argv=None):
             ap.error("features needs --signals and --out-dir")
         features(a.signals, a.out_dir, sample_rate=a.sample_rate)
         return 0
+    if a.command == "preprocess":
+        if not a.wav or not a.out_dir:
+            ap.error("preprocess needs --wav and --out-dir")
+        return 0 if preprocess(a.wav, a.out_dir, sample_rate=a.sample_rate) is not None else 1
+    if a.command == "recognise":
+        if not a.wav:
+            ap.error("recognise needs --wav")
+        return 0 if recognise(a.wav, base_dir=a.data, model_dir=a.models, sample_rate=a.sample_rate) is not None else 1
     if a.command == "codebook":
         if not a.frames or not a.out:
             ap.error("codebook needs --frames and --out")

@@ -47,7 +47,9 @@ extern "C" {
                                  hmmbw_mfcc_tables are new entry points of version 5: an older library lacks the
                                  symbols; hmmbw_align is a new entry point of version 5: an older library lacks
                                  the symbol; hmmbw_align_optional and hmmbw_embedded_train_optional are new
-                                 entry points of version 5: an older library lacks the symbols) */
+                                 entry points of version 5: an older library lacks the symbols; hmmbw_preprocess
+                                 and hmmbw_window_overlap are new entry points of version 5: an older library
+                                 lacks the symbols) */
 
 #define HMMBW_OK 0
 #define HMMBW_E_INVALID (-1)        /* bad argument (shape, range, null pointer)             */
@@ -626,6 +628,54 @@ int hmmbw_mfcc_tables(int frame_len, double sample_rate, int n_mels, int n_mfcc,
 int hmmbw_mfcc(void *stream, const double *samples, int64_t n_samples, const int64_t *frame_starts, int64_t n_frames,
                int frame_len, const double *window, const double *twiddle, const double *mel, int n_mels,
                const double *dct, int n_mfcc, double amin, double top_db, double *out, int64_t out_stride);
+
+/* ---- Signal conditioning: the processed signal hmmbw_mfcc reads, from the raw recording ----
+ * The reference's preemphasis.py (filter_signal :174-183, slice_signal :222-294) and, for the live recogniser,
+ * HMM/live_testing.py (slice_signal :48-120 with two pairs of thresholds, do_preemphasis :163-184) with
+ * preemphasis.hamming_window (:189-212).  All arithmetic is fp64.  For a recording x[0 .. n):
+ *   filter  y[0] = 0, y[i] = x[i] - fl(coeff x[i-1]): the product rounded on its own, never fused into the subtraction
+ *           (the reference's bits for int16 and float64 recordings; its float32 arithmetic for a float32 recording
+ *           under NumPy 2 is not reproduced: upload such a recording as doubles);
+ *   frames  nf = trunc((n - win) / hop) + 1; frame i < nf - 1 is y[i hop, i hop + win), the last one y[(nf - 1) hop,
+ *           n - 1): it spares the last sample and has win - 1 .. win + hop - 2 samples;
+ *           power[i] = sum f^2 / len(f), zcr[i] = 1/2 sum_j |sign(f[j+1]) - sign(f[j])|, sign(0) = 0;
+ *   bounds  factors = (zf, pf, zl, pl); keep_first[i] = zcr[i] > zf max zcr and power[i] > pf max power, keep_last the
+ *           same with (zl, pl), all comparisons strict, a negative zcr factor switching that test off.  If a frame
+ *           passes keep_first: first = the first of them, last = the LAST frame that passes keep_last (first, if none
+ *           does: the reference raises there); otherwise first = 0, last = nf.  bounds_out[r] = (first hop, last hop),
+ *           relative to the recording and never past n: the end is the START of the last kept frame, as in the
+ *           reference.  Batch mode (preemphasis.py) is (-1, 0.015, -1, 0.015), live mode (0.08, 0.15, 0.03, 0.10).
+ * hmmbw_preprocess: DEVICE pointers samples (fp64 for HMMBW_SAMPLES_F64, int16 for HMMBW_SAMPLES_I16: a .wav file's own
+ * samples, a quarter of the bytes to upload), rec_offsets int64 [n_rec + 1] ascending from 0, filtered_out fp64, one
+ * value per input sample, not overlapping samples: y of every whole recording (nothing is compacted; the trimmed signal is the slice bounds_out
+ * names), bounds_out int64 [n_rec][2], stats_out fp64 [sum nf][2] (zcr, power) per frame in recording order, or NULL.
+ * factors is a HOST array of 4.  rec_offsets_host is a HOST copy of rec_offsets or NULL: with it the call checks the
+ * lengths before it launches anything; without it a recording that has no frame gets bounds (0, 0) and no row of
+ * stats_out.  One kernel on `stream` (hipStream_t, NULL = legacy default), one workgroup per recording; nothing waits
+ * on the host.  No index leaves a recording's [rec_offsets[r], rec_offsets[r+1]) whatever the samples are; with
+ * non-finite samples the statistics and bounds are unspecified (but within the recording).  A requested stats_out
+ * costs every workgroup a pass over the offsets before it.
+ * HMMBW_E_INVALID: a null pointer (but stats_out, rec_offsets_host), n_rec < 0, an unknown sample_kind, win < 2,
+ * hop < 1, hop > win, a NaN coefficient or factor; with rec_offsets_host: offsets that do not ascend from 0, a
+ * recording with nf < 1 (n <= win - hop; 160 samples at 16 kHz) or n < 2: the reference raises there too.
+ * HMMBW_E_UNSUPPORTED: win > 65536, n_rec >= 2^31, more than 2^46 samples.  n_rec == 0 returns HMMBW_OK. */
+#define HMMBW_SAMPLES_F64 0
+#define HMMBW_SAMPLES_I16 1
+int hmmbw_preprocess(void *stream, const void *samples, int sample_kind, const int64_t *rec_offsets,
+                     const int64_t *rec_offsets_host, int64_t n_rec, double coeff, int win, int hop,
+                     const double *factors, double *filtered_out, int64_t *bounds_out, double *stats_out);
+/* The live recogniser's overlapping window, in place on t = samples[rec_offsets[r] + start_r, .. + finish_r) of m
+ * samples, (start, finish) read from the DEVICE array bounds [n_rec][2] (hmmbw_preprocess's bounds_out: the two calls
+ * go back to back on one stream), with the DEVICE table window [wlen]:
+ *   q = trunc((m - wlen) / whop) + 1;  for i < q: t[i whop, i whop + wlen) *= window (clipped to m);
+ *   if q >= 0: t[q whop, m - 1) *= window[0 ..): a partial frame that spares the last sample;  q < 0: nothing.
+ * Per sample that is a product over the frames that cover it, taken in ascending frame order, which reproduces the
+ * reference's in-place loop bit for bit.  Samples outside [start, finish) are not touched; bounds that do not lie
+ * within their recording touch nothing.
+ * HMMBW_E_INVALID: a null pointer, n_rec < 0, wlen < 1, whop < 1.  HMMBW_E_UNSUPPORTED: ceil(wlen / whop) > 8,
+ * wlen > 65536, n_rec >= 2^31.  n_rec == 0 returns HMMBW_OK. */
+int hmmbw_window_overlap(void *stream, double *samples, const int64_t *rec_offsets, const int64_t *bounds,
+                         int64_t n_rec, const double *window, int wlen, int whop);
 
 /* ---- Groups: several models of one shape, one launch per EM iteration / per scoring pass ----
  * The reference trains its word models one after another (train_hmm, HMM/main.py:147-152, calling
