@@ -14,10 +14,9 @@ import pytest
 
 import preprocess_ref as R
 from conftest import GOLDEN
+from preprocess_gpu import MODES, check_against, p as _p, preprocess as _preprocess
 
 pytestmark = pytest.mark.gpu
-
-MODES = {"batch": (R.BATCH, False, "batch_bounds", "batch_trimmed"), "live": (R.LIVE, True, "live_bounds", "live_windowed")}
 
 
 @pytest.fixture(scope="module", autouse=True)
@@ -41,58 +40,8 @@ def golden():
     return np.load(os.path.join(GOLDEN, "preprocess.npz"))
 
 
-def _p(t):
-    return ctypes.c_void_p(t.data_ptr())
-
-
-def _preprocess(signals, factors, as_f64, host_offsets=True, win=320, hop=160, stats=True):
-    """hmmbw_preprocess on the concatenated columns; returns (status, y, bounds, stats, offsets) as host arrays"""
-    import torch
-
-    from hmm_training_amd import _lib
-    cols = [R.column(s) for s in signals]
-    offs = np.concatenate([[0], np.cumsum([len(c) for c in cols])]).astype(np.int64)
-    x = np.concatenate(cols)
-    x = x.astype(np.float64) if as_f64 else x.astype(np.int16)
-    tx, toff = torch.from_numpy(x).cuda(), torch.from_numpy(offs).cuda()
-    y = torch.full((len(x),), -7.0, dtype=torch.float64, device="cuda")
-    bounds = torch.full((len(cols), 2), -7, dtype=torch.int64, device="cuda")
-    nf = sum(max(R.frame_count(len(c), win, hop), 0) for c in cols) if 1 <= hop else 0
-    st = torch.full((max(nf, 1), 2), -7.0, dtype=torch.float64, device="cuda")
-    fac = np.array(factors, dtype=np.float64)
-    rc = _lib.lib().hmmbw_preprocess(ctypes.c_void_p(torch.cuda.current_stream().cuda_stream), _p(tx),
-                                     _lib.SAMPLES_F64 if as_f64 else _lib.SAMPLES_I16, _p(toff),
-                                     ctypes.c_void_p(offs.ctypes.data) if host_offsets else None, len(cols), R.COEFF,
-                                     win, hop, ctypes.c_void_p(fac.ctypes.data), _p(y), _p(bounds),
-                                     _p(st) if stats else None)
-    torch.cuda.synchronize()
-    return rc, y.cpu().numpy(), bounds.cpu().numpy(), st.cpu().numpy()[:nf], offs
-
-
 def _check_against(names, cases, mode, y, bounds, stats, offs, trimmed=None):
-    factors, window, _, _ = MODES[mode]
-    pos = 0
-    for r, name in enumerate(names):
-        x, ref = cases[name]
-        want = ref[mode]
-        lo, hi = offs[r], offs[r + 1]
-        if y is not None:
-            # the whole of the recording, bit for bit: a fused multiply-add fails here, and so does a first sample
-            # that saw its neighbour's last one
-            assert np.array_equal(y[lo:hi], want["y"]), name
-            assert y[lo] == 0.0
-        assert bounds[r].tolist() == [want["start"], want["finish"]], name
-        nf = len(want["zcr"])
-        assert np.array_equal(stats[pos:pos + nf, 0], want["zcr"]), name
-        power = stats[pos:pos + nf, 1]
-        scale = np.where(want["power"] > 0, want["power"], 1.0)
-        rel = float((np.abs(power - want["power"]) / scale).max())
-        assert rel <= R.POWER_RTOL, (name, rel)
-        pos += nf
-        if trimmed is not None:
-            assert trimmed[r].shape == (len(want["out"]), 1) and trimmed[r].dtype == np.float64
-            assert np.array_equal(trimmed[r][:, 0], want["out"]), name
-    assert pos == len(stats)
+    check_against([cases[n][1][mode] for n in names], y, bounds, stats, offs, trimmed, names=names)
 
 
 # --------------------------------------------------------------------------------------------------------------

@@ -128,6 +128,180 @@ def test_window_restatement_shapes():
 
 
 # --------------------------------------------------------------------------------------------------------------
+# 3b. other geometries: the reference at 8, 22.05 and 44.1 kHz (tests/golden/preprocess_rates.npz), the margin
+#     condition of every input the GPU shape tests use (tests/test_gpu_preprocess_shapes.py), other window tables
+# --------------------------------------------------------------------------------------------------------------
+@pytest.fixture(scope="module")
+def golden_rates():
+    return np.load(os.path.join(GOLDEN, "preprocess_rates.npz"))
+
+
+def test_power_rtol():
+    assert R.power_rtol(478) <= R.POWER_RTOL and R.power_rtol(1438) <= 3.2e-13 and R.power_rtol(1438) > 3.19e-13
+    assert R.longest_frame(R.GOLDEN_LENGTHS) == 478 and R.longest_frame([1322], 882, 441) == 1321
+    assert R.longest_frame([882 * 6 + 5], 882, 441) == 886 and R.longest_frame([883], 882, 441) == 882
+
+
+def test_golden_rates_file_holds_the_generator_inputs(golden_rates):
+    cases = R.rate_inputs()
+    assert [n for n, _, _ in cases] == list(golden_rates["names"]) and len(cases) == 12
+    assert [R.rate_geometry(sr) for sr in R.RATES] == [(160, 80), (441, 220), (882, 441)]
+    for name, sr, x in cases:
+        assert x.dtype == np.int16 and np.array_equal(x, golden_rates[f"{name}/input"])
+        assert int(golden_rates[f"{name}/sample_rate"]) == sr
+        win, hop = R.rate_geometry(sr)
+        n, nf = len(x), len(golden_rates[f"{name}/zcr"])
+        assert nf == R.frame_count(n, win, hop)
+        if n < win + hop:  # one frame: bounds (0, 0)
+            assert nf == 1 and golden_rates[f"{name}/batch_bounds"].tolist() == [0, 0]
+            assert golden_rates[f"{name}/live_bounds"].tolist() == [0, 0]
+        assert (f"{name}/live_windowed" in golden_rates) == (int(golden_rates[f"{name}/windowed_raised"]) == 0)
+    assert os.path.getsize(os.path.join(GOLDEN, "preprocess_rates.npz")) < 200 << 10
+    for sr in R.RATES:  # the longest possible last frame is there, and a trim that is interior
+        win, hop = R.rate_geometry(sr)
+        assert R.longest_frame([win + hop - 1], win, hop) == win + hop - 2
+        b = golden_rates[f"sr{sr}_n{6 * win + 5}/batch_bounds"]
+        assert 0 < b[0] < b[1] < 6 * win + 5 - hop
+
+
+@pytest.mark.parametrize("name", [n for n, _, _ in R.rate_inputs()])
+def test_restatement_against_golden_rates(golden_rates, name):
+    g = lambda k: golden_rates[f"{name}/{k}"]  # noqa: E731
+    x, sr = g("input"), int(g("sample_rate"))
+    win, hop = R.rate_geometry(sr)
+    rtol = R.power_rtol(R.longest_frame([len(x)], win, hop))
+    for factors, window, bkey, okey in ((R.BATCH, False, "batch_bounds", "batch_trimmed"),
+                                        (R.LIVE, True, "live_bounds", "live_windowed")):
+        got = R.preprocess(x, factors, window, win=win, hop=hop)
+        assert [got["start"], got["finish"]] == g(bkey).tolist()
+        assert np.array_equal(got["zcr"], g("zcr"))
+        rel = np.abs(got["power"] - g("power")) / g("power")
+        assert rel.max() <= rtol
+        if window and int(g("windowed_raised")):  # the reference has no output there; the restatement clips
+            assert 192 < len(got["out"]) < 320
+            continue
+        want = g(okey)
+        assert want.shape == (len(got["out"]), 1)
+        assert np.array_equal(got["out"], want[:, 0])
+    by_rate = R.preprocess(x, R.LIVE, True, sr=sr)  # the sample rate alone gives the same geometry
+    assert (by_rate["start"], by_rate["finish"]) == (got["start"], got["finish"]) and np.array_equal(by_rate["power"], got["power"])
+
+
+def test_margin_condition_other_geometries(golden_rates):
+    """the condition of test_margin_condition for every input of tests/test_gpu_preprocess_shapes.py and of
+    preprocess_rates.npz, each at its own geometry"""
+    worst = {}
+
+    def check(tag, x, win, hop):
+        _, power = R.frame_stats(R.filter_signal(x), win, hop)
+        for factors in (R.BATCH, R.LIVE):
+            m = R.power_margin(power, factors)
+            worst[tag] = min(worst.get(tag, np.inf), m)
+            assert m > R.MARGIN, (tag, win, hop, factors, m)
+
+    for name, sr, x in R.rate_inputs():
+        check(f"rate {sr}", x, *R.rate_geometry(sr))
+        for factors in (R.BATCH, R.LIVE):  # and on the reference's own figures
+            assert R.power_margin(golden_rates[f"{name}/power"], factors) > R.MARGIN
+    for win, hop in R.GEOMETRIES:
+        for x in R.geometry_inputs(win, hop):
+            check(f"geometry {win}/{hop}", x, win, hop)
+    for n_rec in R.BATCH_SIZES:
+        for x in R.batch_inputs(n_rec):
+            check(f"batch of {n_rec}", x, R.WIN, R.HOP)
+    for name, x in R.extreme_inputs():
+        check(name, x, R.WIN, R.HOP)
+    for x in R.nonfinite_batch()[::2]:  # the finite two
+        check("neighbours of the non-finite recording", x, R.WIN, R.HOP)
+    for tag, m in worst.items():
+        print(f"smallest relative distance of a power from a threshold, {tag}: {m:.3g}")
+    print("smallest of all:", min(worst.values()))
+
+
+def test_tie_inputs_are_exact():
+    """the exact-tie recordings do not need the margin: their powers are exact doubles in any summation order, and
+    the ties are the deliberate ones; every other frame is farther than MARGIN from every threshold"""
+    fr = R.tie_frames()
+    assert all(f.dtype == np.int16 and len(f) == 64 and f[0] == 0 and f[-1] == 0 for f in fr.values())
+    assert np.all(fr["loud"] % 2 == 0) and np.array_equal(fr["half"] * 2, fr["loud"])
+    cases = R.tie_inputs()
+    assert [c[0] for c in cases] == ["half_first", "half_last", "cross_first", "cross_last"]
+    for name, x, at, loud in cases:
+        y = R.filter_signal(x, R.TIE_COEFF)
+        assert np.array_equal(y * 2, np.round(y * 2)) and (y * y).sum() * 4 < 2.0 ** 53
+        zcr, power = R.frame_stats(y, R.TIE_WIN, R.TIE_WIN)
+        nf = len(zcr)
+        assert nf == len(x) // 64 and power[-1] == 0.0 and zcr[-1] == 0.0 and len(x) % 64 == 37
+        assert power.max() == power[loud] and zcr.max() == zcr[loud] == 62.0
+        # sums in another order: the same bits
+        sl = R.frame_slices(len(y), R.TIE_WIN, R.TIE_WIN)
+        assert all(float(np.sum((y[a:b] * y[a:b])[::-1])) / (b - a) == power[i] for i, (a, b) in enumerate(sl))
+        if name.startswith("half"):
+            assert power[at] == 0.25 * power[loud] and zcr[at] == zcr[loud]
+        else:
+            assert zcr[at] == 0.5 * zcr[loud] and 0.0 < power[at] < 1e-4 * power[loud]
+        for factors in R.TIE_FACTORS:
+            for pf in {factors[1], factors[3]}:
+                d = np.abs(power - pf * power.max())
+                on = np.flatnonzero(d == 0.0).tolist()
+                if pf == 0.0:
+                    assert on == [i for i in range(nf) if power[i] == 0.0] and len(on) >= 2  # the silent frames
+                elif pf == 0.25:
+                    assert on == ([at] if name.startswith("half") else [])
+                else:
+                    assert on == [loud]
+                assert np.all(d[d > 0.0] > R.MARGIN * max(pf, 1e-3) * power.max())
+    # what the strict comparisons decide
+    want = {"half_first": [(128, 128), (0, 128), (0, 256), (0, 128)], "half_last": [(64, 64), (64, 192), (0, 320), (64, 192)],
+            "cross_first": [(128, 128), (128, 128), (0, 256), (0, 128)],
+            "cross_last": [(64, 64), (64, 64), (0, 320), (64, 192)]}
+    for name, x, at, loud in cases:
+        got = [R.preprocess(x, f, win=64, hop=64, coeff=0.5) for f in R.TIE_FACTORS]
+        assert [(g["start"], g["finish"]) for g in got] == want[name]
+        assert [g["else_branch"] for g in got] == [False, False, True, False]
+
+
+def _window_loop(t, w, whop):
+    """hamming_window's loop, element by element: q full frames in ascending order, each clipped to the signal, then
+    the partial frame from q whop that spares the last sample"""
+    t = [float(v) for v in t]
+    m, wlen = len(t), len(w)
+    q = int((m - wlen) / whop) + 1  # Python's int(): toward zero
+    for i in range(q + 1):
+        start = i * whop
+        stop = m - 1 if i == q else min(start + wlen, m)
+        for j in range(start, stop):
+            t[j] = t[j] * float(w[j - start])
+    return np.array(t, dtype=np.float64)
+
+
+@pytest.mark.parametrize("wlen,whop", R.WINDOW_TABLES)
+def test_window_restatement_other_tables(wlen, whop):
+    w = R.random_table(wlen)
+    rng = np.random.default_rng(5)
+    lengths = R.window_lengths(wlen, whop)
+    assert {0, 1, wlen, wlen + whop + 1, 3 * wlen + 1} <= set(lengths)
+    if whop >= 2:  # a negative quotient that truncation and flooring round differently
+        assert any(m < wlen and (m - wlen) % whop != 0 for m in lengths)
+    for m in lengths:
+        t = rng.normal(size=m) * 1000
+        out = R.window_overlap(t, w, whop)
+        assert np.array_equal(out, _window_loop(t, w, whop)), m
+        q, part = R.window_frames(m, wlen, whop)
+        assert q == int((m - wlen) / whop) + 1 and 0 <= part < max(wlen, 1)
+        if q < 0:
+            assert np.array_equal(out, t)
+        elif m > 1 and not (q >= 1 and (q - 1) * whop + wlen >= m):
+            assert out[m - 1] == t[m - 1]  # the last sample is spared unless a clipped full frame reaches it
+    if whop > wlen:  # gaps between the frames stay as they are
+        t = rng.normal(size=3 * whop + 2)
+        out = R.window_overlap(t, w, whop)
+        for i in range(3):
+            assert np.array_equal(out[i * whop + wlen:(i + 1) * whop], t[i * whop + wlen:(i + 1) * whop])
+            assert not np.array_equal(out[i * whop:i * whop + wlen], t[i * whop:i * whop + wlen])
+
+
+# --------------------------------------------------------------------------------------------------------------
 # 4. preproc_plan.hpp under the sanitizers (a stand-alone program: nothing is loaded into Python)
 # --------------------------------------------------------------------------------------------------------------
 @pytest.fixture(scope="module")
